@@ -13,6 +13,12 @@ Launched by the driver as
 Prints ONE JSON line from rank 0 (whole-job aggregate tokens/s).
 Synthetic data (random token ids), random-init weights, bf16 compute,
 fp32 master weights + fused HIP AdamW.
+
+A plain run does only what the headline figure needs: set up, warm up, time
+``--steps`` steps, print the line.  ``--dump-outputs DIR`` also writes what
+the last timed step computed (see bench_outputs.py).  Everything else the
+benchmark measures (today: the NaiveDdp-vs-torch-DDP step-time comparison on
+the dp>1 GPT-2 layouts) runs only with ``--full``.
 """
 
 from __future__ import annotations
@@ -50,7 +56,18 @@ def parse_args():
                          "(dp/tp path only; ignored when pp > 1)")
     ap.add_argument("--micro-batches", type=int, default=8,
                     help="micro-batches per step when PP is active")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed "
+                         "step computed (loss, a seeded sample of the logits "
+                         "and of the updated parameters) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements (NaiveDdp vs "
+                         "torch DDP step time on the dp>1 GPT-2 layouts); a "
+                         "plain run times the headline steps only")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
 
 
 # dp scales best below 8 GPUs (grad all-reduce overlaps with backward;
@@ -130,6 +147,13 @@ def main():
         result = run_pp_bench(args, cfg, dev, dtype, dp, pp, tp)
     else:
         result = run_dp_tp_bench(args, cfg, dev, dtype, dp, tp)
+
+    if args.dump_outputs:
+        from bench_outputs import dump_outputs
+        dump_outputs(args.dump_outputs, result["outputs"], rank, world)
+        if world > 1:
+            # no rank tears its process group down while a peer still writes
+            dist.barrier()
 
     if rank == 0:
         B_global = args.batch * dp * args.micro_batches if use_pp \
@@ -248,6 +272,7 @@ def run_dp_tp_bench(args, cfg, dev, dtype, dp, tp):
         opt.zero_grad()
         if ema is not None:
             ema.update()
+        return out
 
     stepper = step
     # hipGraph capture: default ON for the launch-bound small models
@@ -260,14 +285,22 @@ def run_dp_tp_bench(args, cfg, dev, dtype, dp, tp):
         # hipGraph capture: grads must keep stable storage
         from torchdistpackage_amd.utils_graph import GraphedStep
 
+        static_out = {}
+
         def graph_step():
             out = model(x, labels=x)
             out["loss"].backward()
             opt.step()
             opt.zero_grad(set_to_none=False)
+            # only the scalar: holding the logits would pin their block in
+            # the graph's memory pool
+            static_out["loss"] = out["loss"]
 
         gs = GraphedStep(graph_step, warmup=max(args.warmup, 3))
-        stepper = gs.replay
+
+        def stepper():
+            gs.replay()
+            return static_out
 
     for _ in range(args.warmup):
         stepper()
@@ -276,8 +309,9 @@ def run_dp_tp_bench(args, cfg, dev, dtype, dp, tp):
     if dev.type == "cuda":
         torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for _ in range(args.steps - 1):
         stepper()
+    last = stepper()   # what the last timed step hands its caller
     if dev.type == "cuda":
         torch.cuda.synchronize()
     if dist.is_initialized():
@@ -290,12 +324,23 @@ def run_dp_tp_bench(args, cfg, dev, dtype, dp, tp):
         dt = float(t.item())
     result = {"ms_per_step": dt * 1e3}
 
-    # --- NaiveDdp vs TorchDDP step time (headline sub-metric) ----------
+    if args.dump_outputs:
+        from bench_outputs import sample_logits, sample_params
+        outputs = {"loss": last["loss"].reshape(1)}
+        if "logits" in last:
+            outputs["logits"] = sample_logits(last["logits"])
+        outputs["params"] = sample_params(model.parameters())
+        result["outputs"] = outputs
+    del last
+
+    # --- NaiveDdp vs TorchDDP step time (--full sub-metric) -------------
     # best-effort: a failure here must never kill the main bench result
-    try:
-        _compare_torchddp(args, model, dev, dp, x, result)
-    except Exception as e:  # noqa: BLE001
-        print(f"[bench] torchddp comparison skipped: {e}", file=sys.stderr)
+    if args.full:
+        try:
+            _compare_torchddp(args, model, dev, dp, x, result)
+        except Exception as e:  # noqa: BLE001
+            print(f"[bench] torchddp comparison skipped: {e}",
+                  file=sys.stderr)
     return result
 
 

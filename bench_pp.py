@@ -107,15 +107,16 @@ def run_pp_bench(args, cfg, dev, dtype, dp, pp, tp):
         return m(stage_in, labels=labels)
 
     def step():
-        forward_backward(fwd_fn, inputs=x if stage.is_first else None,
-                         num_microbatches=num_mb,
-                         extra_inputs=x if stage.is_last else None)
+        loss = forward_backward(fwd_fn, inputs=x if stage.is_first else None,
+                                num_microbatches=num_mb,
+                                extra_inputs=x if stage.is_last else None)
         if isinstance(stage_ddp, NaiveDdp):
             stage_ddp.reduce_gradients()
         if tp > 1:
             allreduce_sequence_parallel_grads(stage)
         opt.step()
         opt.zero_grad()
+        return loss   # last micro-batch's loss on the last stage, else None
 
     for _ in range(args.warmup):
         step()
@@ -124,8 +125,9 @@ def run_pp_bench(args, cfg, dev, dtype, dp, pp, tp):
     if dev.type == "cuda":
         torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for _ in range(args.steps - 1):
         step()
+    last_loss = step()
     if dev.type == "cuda":
         torch.cuda.synchronize()
     if dist.is_initialized():
@@ -135,4 +137,11 @@ def run_pp_bench(args, cfg, dev, dtype, dp, pp, tp):
         t = torch.tensor([dt], device=dev if dev.type == "cuda" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    return {"ms_per_step": dt * 1e3}
+    result = {"ms_per_step": dt * 1e3}
+    if getattr(args, "dump_outputs", None):   # callers with a bare Args class
+        from bench_outputs import sample_params
+        outputs = {"params": sample_params(stage.parameters())}
+        if last_loss is not None:
+            outputs["loss"] = last_loss.reshape(1)
+        result["outputs"] = outputs
+    return result
