@@ -1,0 +1,251 @@
+"""Split-KV decode-attention kernel (ops/csrc/decode_attn.hip) against the
+CPU fp32 oracle, and the ``attn_impl="hip"`` decode paths against the
+training stack / the default decode path.
+
+Bound for the kernel: max abs error < 3e-2, the project's bound for flash
+forward (test_ops_gpu.py); the oracle runs fp32 math on the same bf16
+inputs and every expected value is asserted |v| < 8, where bf16 output
+rounding alone is <= 2^-6."""
+import pytest
+import torch
+
+from torchdistpackage_amd import ops
+from torchdistpackage_amd.inference import generate
+from torchdistpackage_amd.inference.generate import (_alloc_caches,
+                                                     _gpt2_decode_forward,
+                                                     _llama_decode_forward)
+from torchdistpackage_amd.models.gpt2 import GPT2Config, GPT2Model
+
+pytestmark = pytest.mark.gpu
+
+B, SMAX = 2, 256
+BOUND = 3e-2
+LENGTHS = [1, 63, 64, 65, 128, 200, 256]   # pos0 + 1, chunk edges at 64
+
+
+def _make(Hq, Hkv, D, Sq, seed=0):
+    """bf16 q and caches; the caches are narrowed views of a larger
+    allocation (strides differ from a contiguous cache)."""
+    g = torch.Generator(device="cuda").manual_seed(seed)
+
+    def rn(*shape):
+        return torch.randn(*shape, generator=g, device="cuda",
+                           dtype=torch.bfloat16)
+
+    q = rn(B, Hq, Sq, D)
+    kc = rn(B, Hkv, SMAX + 32, D).narrow(2, 16, SMAX)
+    vc = rn(B, Hkv, SMAX + 48, D).narrow(2, 24, SMAX)
+    assert not kc.is_contiguous() and not vc.is_contiguous()
+    return q, kc, vc
+
+
+def _poison_tail(kc, vc, first_dead):
+    """NaN every cache slot from ``first_dead`` (per batch row) on; the
+    parent allocation's margins around the narrowed view are NaN too."""
+    kb, vb = kc._base.clone(), vc._base.clone()
+    k2 = kb.narrow(2, 16, SMAX)
+    v2 = vb.narrow(2, 24, SMAX)
+    kb[:, :, :16] = float("nan")
+    kb[:, :, 16 + SMAX:] = float("nan")
+    vb[:, :, :24] = float("nan")
+    vb[:, :, 24 + SMAX:] = float("nan")
+    for b, n in enumerate(first_dead):
+        k2[b, :, n:] = float("nan")
+        v2[b, :, n:] = float("nan")
+    return k2, v2
+
+
+def _oracle(q, kc, vc, pos0):
+    pos = pos0.cpu() if torch.is_tensor(pos0) else pos0
+    want = ops.decode_attention(q.float().cpu(), kc.float().cpu(),
+                                vc.float().cpu(), pos)
+    assert want.abs().max().item() < 8
+    return want
+
+
+def _check(q, kc, vc, pos0, split_kv, tag):
+    """Run kernel on a NaN-poisoned copy of the caches, compare to the
+    oracle on the clean ones."""
+    Sq = q.shape[2]
+    if torch.is_tensor(pos0):
+        p = pos0.reshape(-1).tolist()
+        dead = [x + Sq for x in (p if len(p) == B else p * B)]
+    else:
+        dead = [pos0 + Sq] * B
+    k2, v2 = _poison_tail(kc, vc, dead)
+    got = ops.decode_attention(q, k2, v2, pos0, split_kv=split_kv)
+    want = _oracle(q, kc, vc, pos0)
+    assert got.shape == q.shape and got.dtype == torch.bfloat16
+    gotf = got.float().cpu()
+    assert torch.isfinite(gotf).all(), tag
+    err = (gotf - want).abs().max().item()
+    print(f"decode_attention {tag}: max abs err {err:.3e}")
+    assert err < BOUND, (tag, err)
+    return got
+
+
+@pytest.mark.parametrize("D", [64, 128])
+@pytest.mark.parametrize("heads", [(4, 4), (8, 2), (8, 1)])
+def test_kernel_vs_oracle_forced_splits(D, heads):
+    Hq, Hkv = heads
+    q, kc, vc = _make(Hq, Hkv, D, 1)
+    for n in LENGTHS:
+        _check(q, kc, vc, n - 1, 64, f"D{D} H{Hq}/{Hkv} len{n}")
+
+
+@pytest.mark.parametrize("split_kv", [None, 256])
+def test_auto_split_and_single_split(split_kv):
+    # None: split chosen from Smax and the CU count; 256: nsplit == 1, the
+    # first kernel writes bf16 itself and no combine launch is made
+    q, kc, vc = _make(8, 2, 128, 1, seed=1)
+    for n in (1, 65, 200, 256):
+        _check(q, kc, vc, n - 1, split_kv, f"split{split_kv} len{n}")
+
+
+@pytest.mark.parametrize("Sq,G", [(1, 1), (2, 1), (4, 1), (2, 4), (4, 4),
+                                  (3, 2)])
+@pytest.mark.parametrize("D", [64, 128])
+def test_rows_per_kv_head_and_causal_alignment(Sq, G, D):
+    # M = G*Sq hits 1, 2, 4, 8, 16 and a padded 6; pos0 = 62 puts the rows'
+    # last visible keys at 62..65, on both sides of the chunk edge
+    q, kc, vc = _make(2 * G, 2, D, Sq, seed=2)
+    _check(q, kc, vc, 62, 64, f"Sq{Sq} G{G} D{D} pos62")
+    _check(q, kc, vc, 0, 64, f"Sq{Sq} G{G} D{D} pos0")
+    _check(q, kc, vc, SMAX - Sq, 64, f"Sq{Sq} G{G} D{D} full")
+
+
+def test_row_blocking_and_tensor_pos_limit():
+    # G*Sq = 20 > 16: the wrapper issues one call per block of 4 rows
+    q, kc, vc = _make(8, 2, 64, 5, seed=3)
+    _check(q, kc, vc, 61, 64, "blocked Sq5 G4")
+    with pytest.raises(ValueError, match="tensor pos0"):
+        ops.decode_attention(q, kc, vc,
+                             torch.tensor([61], device="cuda"))
+
+
+def test_output_layout():
+    q, kc, vc = _make(8, 2, 128, 3, seed=4)
+    o = ops.decode_attention(q, kc, vc, 100, split_kv=64)
+    flat = o.permute(2, 0, 1, 3).reshape(3, B, 8 * 128)
+    assert flat.is_contiguous() and flat.data_ptr() == o.data_ptr()
+
+
+def test_per_row_lengths():
+    q, kc, vc = _make(8, 2, 128, 2, seed=5)
+    pos = torch.tensor([9, 199], device="cuda")
+    _check(q, kc, vc, pos, 64, "per-row pos [9,199]")
+
+
+def test_tensor_pos_equals_int_pos():
+    q, kc, vc = _make(8, 2, 64, 2, seed=6)
+    a = ops.decode_attention(q, kc, vc, 130, split_kv=64)
+    b = ops.decode_attention(q, kc, vc, torch.tensor([130], device="cuda"),
+                             split_kv=64)
+    assert torch.equal(a, b)
+
+
+def test_unsupported_inputs_raise():
+    q = torch.zeros(1, 2, 1, 96, device="cuda", dtype=torch.bfloat16)
+    kv = torch.zeros(1, 2, 64, 96, device="cuda", dtype=torch.bfloat16)
+    with pytest.raises(ValueError, match="head dim"):
+        ops.decode_attention(q, kv, kv, 0)
+    q = torch.zeros(1, 2, 1, 64, device="cuda")
+    kv = torch.zeros(1, 2, 64, 64, device="cuda")
+    with pytest.raises(TypeError, match="bf16"):
+        ops.decode_attention(q, kv, kv, 0)
+
+
+def test_graph_capture_follows_position_tensor():
+    q, kc, vc = _make(8, 2, 128, 1, seed=7)
+    pos_t = torch.tensor([63], device="cuda")
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        ops.decode_attention(q, kc, vc, pos_t, split_kv=64)
+    torch.cuda.current_stream().wait_stream(s)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        out = ops.decode_attention(q, kc, vc, pos_t, split_kv=64)
+    for p in (63, 64, 65):
+        graph.replay()
+        torch.cuda.synchronize()
+        want = _oracle(q, kc, vc, p)
+        err = (out.float().cpu() - want).abs().max().item()
+        assert err < BOUND, (p, err)
+        pos_t += 1
+
+
+# ---------------------------------------------------------------------------
+# model level: same forms and bounds as test_generate_gpu.py
+# ---------------------------------------------------------------------------
+
+def _teacher_forced(m, fwd, toks, n_kv, prefill):
+    cfg = m.cfg
+    with torch.no_grad():
+        full = m(toks)["logits"].float()        # training stack, (B, T, V)
+    Bt, T = toks.shape
+    caches = _alloc_caches(cfg.n_layer, Bt, n_kv, T, cfg.dim // cfg.n_head,
+                           torch.device("cuda"), torch.bfloat16)
+    pos0, chunk = 0, toks[:, :prefill]
+    while chunk.shape[1] > 0:
+        logits = fwd(m, chunk, caches, pos0, attn_impl="hip").float()
+        pos = pos0 + chunk.shape[1] - 1
+        diff = (logits - full[:, pos]).abs().max().item()
+        assert diff < 0.25, (pos, diff)
+        pos0 += chunk.shape[1]
+        chunk = toks[:, pos0:pos0 + 1]
+
+
+def test_gpt2_decode_logits_hip_match_training_path():
+    torch.manual_seed(0)
+    cfg = GPT2Config(vocab_size=50304, n_layer=4, n_head=12, dim=768,
+                     max_seq=64)
+    m = GPT2Model(cfg, device="cuda", dtype=torch.bfloat16).eval()
+    toks = torch.randint(0, cfg.vocab_size, (2, 24), device="cuda")
+    _teacher_forced(m, _gpt2_decode_forward, toks, cfg.n_head, 8)
+
+
+def _tiny_gqa_llama():
+    from torchdistpackage_amd.models.llama import LlamaConfig, LlamaModel
+    torch.manual_seed(0)
+    cfg = LlamaConfig(vocab_size=2048, n_layer=3, n_head=8, n_kv_head=2,
+                      dim=512, ffn_dim=1024, max_seq=64)
+    return LlamaModel(cfg, device="cuda", dtype=torch.bfloat16).eval()
+
+
+def test_llama_decode_logits_hip_match_training_path():
+    m = _tiny_gqa_llama()
+    toks = torch.randint(0, m.cfg.vocab_size, (2, 24), device="cuda")
+    _teacher_forced(m, _llama_decode_forward, toks, m.cfg.n_kv_head, 8)
+
+
+def test_graphed_gpt2_decoder_hip_vs_eager():
+    from torchdistpackage_amd.inference.generate import GraphedGPT2Decoder
+    torch.manual_seed(0)
+    cfg = GPT2Config(vocab_size=50304, n_layer=4, n_head=8, dim=512,
+                     max_seq=64)
+    m = GPT2Model(cfg, device="cuda", dtype=torch.bfloat16).eval()
+    idx = torch.randint(0, cfg.vocab_size, (2, 8), device="cuda")
+    dec = GraphedGPT2Decoder(m, batch=2, max_seq=48, attn_impl="hip")
+    assert dec.mask is None
+    out_g = dec.generate(idx, 24)
+    out_e = generate(m, idx, 24)
+    assert out_g.shape == out_e.shape == (2, 32)
+    assert torch.equal(out_g[:, :12], out_e[:, :12])
+    agree = (out_g == out_e).float().mean().item()
+    assert agree >= 0.8, agree
+
+
+def test_graphed_llama_decoder_hip_vs_eager():
+    from torchdistpackage_amd.inference.generate import GraphedLlamaDecoder
+    m = _tiny_gqa_llama()
+    idx = torch.randint(0, m.cfg.vocab_size, (2, 6), device="cuda")
+    dec = GraphedLlamaDecoder(m, batch=2, max_seq=40, attn_impl="hip")
+    assert dec.mask is None
+    out_g = dec.generate(idx, 20)
+    out_e = generate(m, idx, 20)
+    assert out_g.shape == out_e.shape == (2, 26)
+    assert torch.equal(out_g[:, :12], out_e[:, :12])
+    agree = (out_g == out_e).float().mean().item()
+    assert agree >= 0.8, agree

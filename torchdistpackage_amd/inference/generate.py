@@ -9,8 +9,10 @@ Scope: tp=1 (single device).  At tp=1 the Col/Row parallel linears, SP
 plumbing and vocab-parallel head are all inert, so the training modules'
 weights are reused directly by the ``decode_step`` methods
 (parallel/tensor/attn.py, models/llama.py).  Decode-shaped attention is
-GEMV-like and memory-bound, so it runs eager SDPA over the cache rather
-than the training flash kernel.
+GEMV-like and memory-bound, so the training flash kernel is the wrong tool;
+every path here takes ``attn_impl``: ``"sdpa"`` (eager SDPA over the cache,
+the default) or ``"hip"`` (the split-KV decode kernel,
+ops.decode_attention).  ``None`` reads ``TDPA_DECODE_ATTN``.
 """
 
 from __future__ import annotations
@@ -19,6 +21,7 @@ from typing import List, Optional, Tuple
 
 import torch
 
+from ..ops import decode_attention, resolve_decode_attn_impl
 from ..parallel.tensor import get_tp_size
 
 
@@ -47,7 +50,8 @@ def _sample(logits: torch.Tensor, greedy: bool, temperature: float,
 
 @torch.no_grad()
 def _gpt2_decode_forward(model, idx: torch.Tensor, caches, pos0: int,
-                         all_logits: bool = False):
+                         all_logits: bool = False,
+                         attn_impl: Optional[str] = None):
     """Forward ``idx`` (B, S_new) through the cached stack; returns the last
     position's logits (B, V), or every position's (B, S_new, V) with
     ``all_logits`` (speculative verification needs the whole chunk)."""
@@ -56,7 +60,7 @@ def _gpt2_decode_forward(model, idx: torch.Tensor, caches, pos0: int,
     x = model.embed.wte(idx) + model.embed.wpe(pos)[None, :, :]
     x = x.transpose(0, 1).contiguous()          # (S, B, D)
     for blk, (kc, vc) in zip(model.blocks, caches):
-        x = blk.decode_step(x, kc, vc, pos0)
+        x = blk.decode_step(x, kc, vc, pos0, attn_impl)
     if all_logits:
         return model.head(x)                    # (B, S, V)
     return model.head(x[-1:])[:, -1]            # ln_f + tied head, (B, V)
@@ -64,11 +68,12 @@ def _gpt2_decode_forward(model, idx: torch.Tensor, caches, pos0: int,
 
 @torch.no_grad()
 def _llama_decode_forward(model, idx: torch.Tensor, caches, pos0: int,
-                          all_logits: bool = False):
+                          all_logits: bool = False,
+                          attn_impl: Optional[str] = None):
     B, S = idx.shape
     x = model.embed.tok(idx).transpose(0, 1).contiguous()
     for blk, (kc, vc) in zip(model.blocks, caches):
-        x = blk.decode_step(x, kc, vc, pos0)
+        x = blk.decode_step(x, kc, vc, pos0, attn_impl)
     if all_logits:
         return model.head(x)
     return model.head(x[-1:])[:, -1]
@@ -85,6 +90,11 @@ class _GraphedDecoder:
     single-stream with the decode GEMV kernels).  Host work per token:
     advance the position tensor, open one mask slot, replay.
 
+    ``attn_impl="hip"`` replaces the full-length masked SDPA with
+    ops.decode_attention reading ``pos_t`` on the device: cost follows the
+    valid length instead of the cache capacity, GQA caches are read
+    un-expanded, and no mask is built or maintained.
+
     Greedy only (the argmax lives inside the graph).  Subclasses bind the
     model family; usage::
 
@@ -93,8 +103,9 @@ class _GraphedDecoder:
     """
 
     def __init__(self, model, batch: int, max_seq: int, n_kv: int,
-                 warmup: int = 3):
+                 warmup: int = 3, attn_impl: Optional[str] = None):
         assert get_tp_size() == 1
+        self.attn_impl = resolve_decode_attn_impl(attn_impl)
         assert torch.cuda.is_available()
         self.model = model
         cfg = model.cfg
@@ -107,13 +118,15 @@ class _GraphedDecoder:
                                     hd, dev, dtype)
         self.in_tok = torch.zeros(batch, 1, dtype=torch.long, device=dev)
         self.pos_t = torch.zeros(1, dtype=torch.long, device=dev)
-        self.mask = torch.full((1, 1, 1, max_seq), float("-inf"),
-                               dtype=dtype, device=dev)
         self.pos = 0
+        self.mask = None                # the hip path reads pos_t instead
         # capture with position 0 visible (an all-masked row would NaN);
         # the garbage this warmup writes into cache slot 0 is overwritten
         # by the first prefill()
-        self.mask[..., :1] = 0
+        if self.attn_impl == "sdpa":
+            self.mask = torch.full((1, 1, 1, max_seq), float("-inf"),
+                                   dtype=dtype, device=dev)
+            self.mask[..., :1] = 0
         self._graph = torch.cuda.CUDAGraph()
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
@@ -139,8 +152,9 @@ class _GraphedDecoder:
         assert S0 < self.max_seq
         logits = self._prefill_fwd(idx)
         self.pos = S0
-        self.mask.fill_(float("-inf"))
-        self.mask[..., :S0 + 1] = 0
+        if self.mask is not None:
+            self.mask.fill_(float("-inf"))
+            self.mask[..., :S0 + 1] = 0
         self.pos_t.fill_(S0)
         self.in_tok.copy_(logits.argmax(-1, keepdim=True))
 
@@ -153,7 +167,7 @@ class _GraphedDecoder:
         self._graph.replay()
         self.pos += 1
         self.pos_t += 1
-        if self.pos < self.max_seq:
+        if self.mask is not None and self.pos < self.max_seq:
             self.mask[..., self.pos] = 0
         return tok
 
@@ -167,11 +181,14 @@ class _GraphedDecoder:
 
 
 class GraphedGPT2Decoder(_GraphedDecoder):
-    def __init__(self, model, batch: int, max_seq: int, warmup: int = 3):
-        super().__init__(model, batch, max_seq, model.cfg.n_head, warmup)
+    def __init__(self, model, batch: int, max_seq: int, warmup: int = 3,
+                 attn_impl: Optional[str] = None):
+        super().__init__(model, batch, max_seq, model.cfg.n_head, warmup,
+                         attn_impl)
 
     def _prefill_fwd(self, idx):
-        return _gpt2_decode_forward(self.model, idx, self.caches, 0)
+        return _gpt2_decode_forward(self.model, idx, self.caches, 0,
+                                    attn_impl=self.attn_impl)
 
     @torch.no_grad()
     def _attn(self, attn, x):
@@ -190,8 +207,11 @@ class GraphedGPT2Decoder(_GraphedDecoder):
         kc, vc = self._cur_cache
         kc.index_copy_(2, self.pos_t, k)
         vc.index_copy_(2, self.pos_t, v)
-        o = torch.nn.functional.scaled_dot_product_attention(
-            q, kc, vc, attn_mask=self.mask)
+        if self.attn_impl == "hip":
+            o = decode_attention(q, kc, vc, self.pos_t)
+        else:
+            o = torch.nn.functional.scaled_dot_product_attention(
+                q, kc, vc, attn_mask=self.mask)
         o = o.permute(2, 0, 1, 3).reshape(1, B, hl * hd)
         return attn.proj(o)
 
@@ -215,11 +235,14 @@ class GraphedLlamaDecoder(_GraphedDecoder):
     device tensor (ops rope_apply_pos — the host-scalar variant would bake
     one position into the graph), K/V heads expand to Q heads for SDPA."""
 
-    def __init__(self, model, batch: int, max_seq: int, warmup: int = 3):
-        super().__init__(model, batch, max_seq, model.cfg.n_kv_head, warmup)
+    def __init__(self, model, batch: int, max_seq: int, warmup: int = 3,
+                 attn_impl: Optional[str] = None):
+        super().__init__(model, batch, max_seq, model.cfg.n_kv_head, warmup,
+                         attn_impl)
 
     def _prefill_fwd(self, idx):
-        return _llama_decode_forward(self.model, idx, self.caches, 0)
+        return _llama_decode_forward(self.model, idx, self.caches, 0,
+                                     attn_impl=self.attn_impl)
 
     @torch.no_grad()
     def _attn(self, attn, x):
@@ -239,10 +262,13 @@ class GraphedLlamaDecoder(_GraphedDecoder):
         kc, vc = self._cur_cache
         kc.index_copy_(2, self.pos_t, k)
         vc.index_copy_(2, self.pos_t, v)
-        rep = attn.nh_local // attn.nkv_local
-        o = torch.nn.functional.scaled_dot_product_attention(
-            q, kc.repeat_interleave(rep, dim=1),
-            vc.repeat_interleave(rep, dim=1), attn_mask=self.mask)
+        if self.attn_impl == "hip":
+            o = decode_attention(q, kc, vc, self.pos_t)
+        else:
+            rep = attn.nh_local // attn.nkv_local
+            o = torch.nn.functional.scaled_dot_product_attention(
+                q, kc.repeat_interleave(rep, dim=1),
+                vc.repeat_interleave(rep, dim=1), attn_mask=self.mask)
         o = o.permute(2, 0, 1, 3).reshape(1, B, attn.nh_local * hd)
         return attn.wo(o)
 
@@ -262,13 +288,16 @@ class GraphedLlamaDecoder(_GraphedDecoder):
 @torch.no_grad()
 def generate(model, idx: torch.Tensor, max_new_tokens: int,
              greedy: bool = True, temperature: float = 1.0,
-             top_k: Optional[int] = None) -> torch.Tensor:
+             top_k: Optional[int] = None,
+             attn_impl: Optional[str] = None) -> torch.Tensor:
     """Autoregressive generation with KV caches.
 
     Args:
         model: a GPT2Model or LlamaModel (tp=1).
         idx: prompt token ids (B, S0).
         max_new_tokens: number of tokens to append.
+        attn_impl: decode attention, ``"sdpa"`` or ``"hip"``; ``None``
+            reads ``TDPA_DECODE_ATTN`` (default sdpa).
     Returns (B, S0 + max_new_tokens) token ids.
     """
     assert get_tp_size() == 1, "generate() supports tp=1 (single device)"
@@ -287,7 +316,7 @@ def generate(model, idx: torch.Tensor, max_new_tokens: int,
     tokens = idx
     chunk, pos0 = idx, 0
     for _ in range(max_new_tokens):
-        logits = fwd(model, chunk, caches, pos0)
+        logits = fwd(model, chunk, caches, pos0, attn_impl=attn_impl)
         nxt = _sample(logits, greedy, temperature, top_k)
         tokens = torch.cat([tokens, nxt[:, None]], dim=1)
         pos0 += chunk.shape[1]
@@ -297,7 +326,8 @@ def generate(model, idx: torch.Tensor, max_new_tokens: int,
 
 @torch.no_grad()
 def speculative_generate(target, draft, idx: torch.Tensor,
-                         max_new_tokens: int, k: int = 4) -> torch.Tensor:
+                         max_new_tokens: int, k: int = 4,
+                         attn_impl: Optional[str] = None) -> torch.Tensor:
     """Greedy speculative decoding: ``draft`` proposes ``k`` tokens per
     round, ``target`` verifies the whole chunk in ONE forward.  Output is
     EXACTLY the target's greedy generation — the draft only changes how
@@ -328,8 +358,9 @@ def speculative_generate(target, draft, idx: torch.Tensor,
                              next(m.parameters()).dtype)
 
     t_caches, d_caches = caches_of(target), caches_of(draft)
-    lt = t_fwd(target, idx, t_caches, 0)
-    d_fwd(draft, idx, d_caches, 0)
+    attn_impl = resolve_decode_attn_impl(attn_impl)
+    lt = t_fwd(target, idx, t_caches, 0, attn_impl=attn_impl)
+    d_fwd(draft, idx, d_caches, 0, attn_impl=attn_impl)
     tokens = torch.cat([idx, lt.argmax(-1)[:, None]], dim=1)
     produced = 1
     while produced < max_new_tokens:
@@ -339,12 +370,13 @@ def speculative_generate(target, draft, idx: torch.Tensor,
         props = []
         cur = tokens[:, -1:]
         for j in range(kk):
-            dl = d_fwd(draft, cur, d_caches, base + j)
+            dl = d_fwd(draft, cur, d_caches, base + j, attn_impl=attn_impl)
             cur = dl.argmax(-1)[:, None]
             props.append(cur)
         # ---- target verifies [last_committed, props[:-1]] in one chunk
         chunk = torch.cat([tokens[:, -1:]] + props[:-1], dim=1)  # (1, kk)
-        tl = t_fwd(target, chunk, t_caches, base, all_logits=True)
+        tl = t_fwd(target, chunk, t_caches, base, all_logits=True,
+                   attn_impl=attn_impl)
         truth = tl.argmax(-1)             # (1, kk): token after each prefix
         a = 0
         while a < kk - 1 and bool(truth[0, a] == props[a][0, 0]):

@@ -130,12 +130,15 @@ class LlamaAttention(nn.Module):
 
     @torch.no_grad()
     def decode_step(self, x: torch.Tensor, k_cache: torch.Tensor,
-                    v_cache: torch.Tensor, pos0: int) -> torch.Tensor:
+                    v_cache: torch.Tensor, pos0: int,
+                    attn_impl: Optional[str] = None) -> torch.Tensor:
         """KV-cache inference step (tp=1 only; see inference/generate.py).
         RoPE is applied at the absolute positions ``pos0..pos0+S_new``; the
-        cache holds rotated K, so cached entries are reused verbatim.  K/V
-        heads are expanded to Q heads for eager SDPA (decode is GEMV-shaped,
-        memory-bound — the flash kernel is the training-shape path)."""
+        cache holds rotated K, so cached entries are reused verbatim.
+        ``attn_impl="sdpa"`` expands K/V heads to Q heads for eager SDPA;
+        ``"hip"`` runs the split-KV decode kernel on the un-expanded caches
+        (ops.decode_attention); ``None`` reads ``TDPA_DECODE_ATTN``."""
+        from ..ops import decode_attention, resolve_decode_attn_impl
         from ..parallel.tensor.attn import _cached_sdpa
         S, B, _ = x.shape
         q = fast_linear(x, self.wq.weight)
@@ -150,10 +153,15 @@ class LlamaAttention(nn.Module):
         v = view4(v, self.nkv_local)
         k_cache[:, :, pos0:pos0 + S] = k
         v_cache[:, :, pos0:pos0 + S] = v
-        rep = self.nh_local // self.nkv_local
-        o = _cached_sdpa(q, k_cache.repeat_interleave(rep, dim=1),
-                         v_cache.repeat_interleave(rep, dim=1), pos0,
-                         self.causal)
+        if resolve_decode_attn_impl(attn_impl) == "hip":
+            assert self.causal or S == 1, \
+                "decode_attention is causal over the new rows"
+            o = decode_attention(q, k_cache, v_cache, pos0)
+        else:
+            rep = self.nh_local // self.nkv_local
+            o = _cached_sdpa(q, k_cache.repeat_interleave(rep, dim=1),
+                             v_cache.repeat_interleave(rep, dim=1), pos0,
+                             self.causal)
         o = o.permute(2, 0, 1, 3).reshape(S, B, self.nh_local * self.hd)
         return self.wo(o)
 
@@ -209,9 +217,9 @@ class LlamaBlock(nn.Module):
         return x
 
     @torch.no_grad()
-    def decode_step(self, x, k_cache, v_cache, pos0: int):
+    def decode_step(self, x, k_cache, v_cache, pos0: int, attn_impl=None):
         x = x + self.attn.decode_step(self.attn_norm(x), k_cache, v_cache,
-                                      pos0)
+                                      pos0, attn_impl)
         return x + self.mlp(self.mlp_norm(x))
 
 

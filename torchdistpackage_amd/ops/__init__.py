@@ -525,6 +525,123 @@ def gqa_attention(q, k, v, causal: bool = True, scale: float = None):
     return o.permute(2, 0, 1, 3).reshape(S, B, H * D)
 
 
+# ---------------------------------------------------------------------------
+# decode attention over a KV cache (split-KV flash-decoding kernel)
+# ---------------------------------------------------------------------------
+
+_DECODE_MAX_ROWS = 16   # query rows per kv head one kernel call serves
+
+
+def resolve_decode_attn_impl(attn_impl: Optional[str] = None) -> str:
+    """``"sdpa"`` (eager SDPA over the cache, the default) or ``"hip"``
+    (:func:`decode_attention`).  ``None`` reads ``TDPA_DECODE_ATTN``
+    (``0`` -> sdpa, ``1`` -> hip)."""
+    if attn_impl is None:
+        attn_impl = "hip" if os.environ.get("TDPA_DECODE_ATTN", "0") == "1" \
+            else "sdpa"
+    if attn_impl not in ("sdpa", "hip"):
+        raise ValueError(f"attn_impl must be 'sdpa' or 'hip', got "
+                         f"{attn_impl!r}")
+    return attn_impl
+
+
+def _decode_attention_ref(q, k_cache, v_cache, pos0, scale):
+    """Exact fp32 math, no K/V head expansion: the numerics oracle."""
+    B, Hq, Sq, D = q.shape
+    Hkv, Smax = k_cache.shape[1], k_cache.shape[2]
+    G = Hq // Hkv
+    if torch.is_tensor(pos0):
+        pos = pos0.reshape(-1).to(device=q.device, dtype=torch.long)
+        pos = pos.expand(B) if pos.numel() == 1 else pos
+    else:
+        if pos0 < 0 or pos0 + Sq > Smax:
+            raise ValueError(f"decode_attention: pos0={pos0} with Sq={Sq} "
+                             f"outside the cache (Smax={Smax})")
+        pos = torch.full((B,), int(pos0), dtype=torch.long, device=q.device)
+    pos = pos.clamp(0, Smax - Sq)
+    L = int(pos.max()) + Sq                       # nothing beyond is touched
+    kf = k_cache[:, :, :L].float()
+    vf = v_cache[:, :, :L].float()
+    j = torch.arange(L, device=q.device)
+    # keys no row of this batch element sees must not reach the result,
+    # whatever they hold (0 * NaN): zero V there
+    live = j[None, :] < (pos[:, None] + Sq)                       # (B, L)
+    vf = torch.where(live[:, None, :, None], vf, torch.zeros_like(vf))
+    qf = q.float().reshape(B, Hkv, G * Sq, D)     # rows of one kv head
+    s = torch.matmul(qf, kf.transpose(-1, -2)) * scale            # (B,Hkv,M,L)
+    row = torch.arange(G * Sq, device=q.device) % Sq
+    vis = j[None, None, :] <= (pos[:, None, None] + row[None, :, None])
+    s = s.masked_fill(~vis[:, None], float("-inf"))
+    o = torch.matmul(torch.softmax(s, dim=-1), vf)
+    return o.reshape(B, Hq, Sq, D).to(q.dtype)
+
+
+def decode_attention(q: torch.Tensor, k_cache: torch.Tensor,
+                     v_cache: torch.Tensor, pos0, scale: float = None,
+                     split_kv: Optional[int] = None) -> torch.Tensor:
+    """Attention of new query rows against a KV cache.
+
+    q (B, Hq, Sq, D); k_cache / v_cache (B, Hkv, Smax, D) with
+    ``Hq % Hkv == 0`` (un-expanded GQA caches; last dim contiguous, other
+    strides free).  ``pos0`` is the absolute position of query row 0: a host
+    int, or an int64 tensor with 1 or B elements that the kernel reads at
+    run time (hipGraph-capturable; B elements = per-row lengths).  Row ``i``
+    attends to cache positions ``[0, pos0+i]``; nothing at or beyond
+    ``pos0+Sq`` reaches the result.
+
+    Returns (B, Hq, Sq, D), a strided view of an (Sq, B, Hq*D) buffer, so
+    ``o.permute(2, 0, 1, 3).reshape(Sq, B, Hq*D)`` is a view.
+
+    GPU bf16 runs the split-KV HIP kernel (head dim 64 or 128; anything
+    else raises — there is no composite path).  CPU tensors of any float
+    dtype run exact fp32 math (the oracle).  ``split_kv`` overrides the KV
+    chunk length per workgroup (tests; default chosen from Smax).
+    """
+    B, Hq, Sq, D = q.shape
+    Hkv = k_cache.shape[1]
+    if Hq % Hkv != 0:
+        raise ValueError(f"decode_attention: Hq={Hq} not a multiple of "
+                         f"Hkv={Hkv}")
+    if scale is None:
+        scale = 1.0 / math.sqrt(D)
+    if not q.is_cuda:
+        o = _decode_attention_ref(q, k_cache, v_cache, pos0, scale)
+        o_buf = o.permute(2, 0, 1, 3).contiguous()      # (Sq, B, Hq, D)
+        return o_buf.permute(1, 2, 0, 3)
+    if q.dtype != torch.bfloat16:
+        raise TypeError("decode_attention: the GPU kernel is bf16-only, got "
+                        f"{q.dtype}")
+    if D not in (64, 128):
+        raise ValueError("decode_attention: the GPU kernel covers head dim "
+                         f"64 and 128, got {D}")
+    G = Hq // Hkv
+    if G > _DECODE_MAX_ROWS:
+        raise ValueError(f"decode_attention: Hq/Hkv={G} exceeds the "
+                         f"kernel's {_DECODE_MAX_ROWS} rows per kv head")
+    e = ext("decode_attention")
+    o_buf = torch.empty(Sq, B, Hq * D, dtype=q.dtype, device=q.device)
+    o4 = o_buf.view(Sq, B, Hq, D).permute(1, 2, 0, 3)
+    skv = int(split_kv or 0)
+    if torch.is_tensor(pos0):
+        if G * Sq > _DECODE_MAX_ROWS:
+            raise ValueError(
+                f"decode_attention: (Hq/Hkv)*Sq={G * Sq} exceeds "
+                f"{_DECODE_MAX_ROWS} rows per kv head; with a tensor pos0 "
+                "the call cannot be split on the host — pass an int pos0 "
+                "or fewer query rows")
+        e.decode_attention(q, k_cache, v_cache, o4, pos0, 0, float(scale),
+                           skv)
+        return o4
+    pos0 = int(pos0)
+    rows = _DECODE_MAX_ROWS // G          # query rows per kernel call
+    for r0 in range(0, Sq, rows):
+        r1 = min(r0 + rows, Sq)
+        e.decode_attention(q[:, :, r0:r1], k_cache, v_cache,
+                           o4[:, :, r0:r1], None, pos0 + r0, float(scale),
+                           skv)
+    return o4
+
+
 class _CrossEntropyFn(torch.autograd.Function):
     """Fused mean cross-entropy on bf16 logits (one online-LSE pass fwd, one
     dlogits pass bwd) — replaces logits.float()+F.cross_entropy which

@@ -27,6 +27,7 @@ SOURCES = [
     "gemm.hip",
     "rope_swiglu.hip",
     "gemv.hip",
+    "decode_attn.hip",
 ]
 
 

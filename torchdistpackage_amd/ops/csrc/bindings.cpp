@@ -60,6 +60,10 @@ torch::Tensor gemv_bf16(torch::Tensor x, torch::Tensor W,
                         c10::optional<torch::Tensor> bias);
 torch::Tensor rope_apply_pos(torch::Tensor x, torch::Tensor cs,
                              torch::Tensor sn, torch::Tensor pos, bool fwd);
+torch::Tensor decode_attention(torch::Tensor q, torch::Tensor k_cache,
+                               torch::Tensor v_cache, torch::Tensor out,
+                               c10::optional<torch::Tensor> pos_t, long pos0,
+                               double scale, long split_kv);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rmsnorm_fwd", &rmsnorm_fwd);
@@ -91,4 +95,5 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ce_partial_fwd", &ce_partial_fwd);
   m.def("gemv_bf16", &gemv_bf16);
   m.def("rope_apply_pos", &rope_apply_pos);
+  m.def("decode_attention", &decode_attention);
 }

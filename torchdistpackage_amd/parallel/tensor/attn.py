@@ -12,11 +12,14 @@ Layout: activations are sequence-first (S, B, D); SP shards dim 0.
 
 from __future__ import annotations
 
+from typing import Optional
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ...ops import fused_qkv_attention
+from ...ops import (decode_attention, fused_qkv_attention,
+                    resolve_decode_attn_impl)
 from .tp_utils import (ColParallelLinear, RowParallelLinear, TpLinear,
                        copy_to_tp_region, gather_from_sequence_parallel_region,
                        get_tp_size, is_sequence_parallel)
@@ -103,14 +106,16 @@ class TpAttention(nn.Module):
 
     @torch.no_grad()
     def decode_step(self, x: torch.Tensor, k_cache: torch.Tensor,
-                    v_cache: torch.Tensor, pos0: int) -> torch.Tensor:
+                    v_cache: torch.Tensor, pos0: int,
+                    attn_impl: Optional[str] = None) -> torch.Tensor:
         """KV-cache inference step (tp=1 only; see inference/generate.py).
 
         x (S_new, B, D) — the new tokens' hidden states; writes their K/V
         into ``k_cache``/``v_cache`` (B, H, max_seq, hd) at ``pos0`` and
-        attends q against positions [0, pos0+S_new).  Decode is
-        memory-bound GEMV-shaped work, so eager SDPA over the cache is the
-        right tool (the flash kernel is the training-shape path).
+        attends q against positions [0, pos0+S_new).  ``attn_impl``:
+        ``"sdpa"`` = eager SDPA over the cache, ``"hip"`` = the split-KV
+        decode kernel (ops.decode_attention); ``None`` reads
+        ``TDPA_DECODE_ATTN`` (default sdpa).
         """
         from ...ops.gemm import linear as fast_linear
         S, B, D = x.shape
@@ -125,7 +130,12 @@ class TpAttention(nn.Module):
         q, k, v = v4(q), v4(k), v4(v)
         k_cache[:, :, pos0:pos0 + S] = k
         v_cache[:, :, pos0:pos0 + S] = v
-        o = _cached_sdpa(q, k_cache, v_cache, pos0, self.causal)
+        if resolve_decode_attn_impl(attn_impl) == "hip":
+            assert self.causal or S == 1, \
+                "decode_attention is causal over the new rows"
+            o = decode_attention(q, k_cache, v_cache, pos0)
+        else:
+            o = _cached_sdpa(q, k_cache, v_cache, pos0, self.causal)
         o = o.permute(2, 0, 1, 3).reshape(S, B, hl * hd)
         return self.proj(o)
 
