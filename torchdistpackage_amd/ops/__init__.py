@@ -129,6 +129,15 @@ class _LayerNormFn(torch.autograd.Function):
             xf = x.float()
             mean = xf.mean(-1, keepdim=True)
             var = xf.var(-1, unbiased=False, keepdim=True)
+            # an fp32 sum of an off-centre row (1000 + randn) leaves the
+            # mean ~D ulps out: such rows get one refinement step (the HIP
+            # kernels draw the same line, mean^2 <= var)
+            off = ~(mean * mean <= var)
+            if off.any():
+                mean2 = mean + (xf - mean).mean(-1, keepdim=True)
+                var2 = (xf - mean2).pow(2).mean(-1, keepdim=True)
+                mean = torch.where(off, mean2, mean)
+                var = torch.where(off, var2, var)
             rstd = torch.rsqrt(var + eps)
             y = ((xf - mean) * rstd * weight.float() + bias.float()).to(x.dtype)
             mean, rstd = mean.squeeze(-1), rstd.squeeze(-1)

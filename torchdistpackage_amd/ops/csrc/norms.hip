@@ -71,15 +71,9 @@ __global__ void rmsnorm_bwd_kernel(const T* __restrict__ dy,
                                    const T* __restrict__ w,
                                    const float* __restrict__ rstd,
                                    T* __restrict__ dx,
-                                   float* __restrict__ dw_partial,
                                    int rows, int D) {
-  // dynamic LDS: [D] floats for the dw accumulator + BLOCK/WAVE scratch
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* dw_lds = (float*)smem;
-  float* scratch = dw_lds + D;
-  for (int i = threadIdx.x; i < D; i += BLOCK) dw_lds[i] = 0.f;
-  __syncthreads();
-
+  // dx only: dw comes from norm_bwd_dwdb_kernel
+  __shared__ float scratch[BLOCK / WAVE];
   for (int row = blockIdx.x; row < rows; row += gridDim.x) {
     const T* dyr = dy + (long)row * D;
     const T* xr = x + (long)row * D;
@@ -97,15 +91,79 @@ __global__ void rmsnorm_bwd_kernel(const T* __restrict__ dy,
       float dyv = load_as_f32(dyr, i);
       float wdy = load_as_f32(w, i) * dyv;
       store_from_f32(dxr, i, r * (wdy - xhat * dot));
-      dw_lds[i] += dyv * xhat;
     }
     __syncthreads();
   }
-  for (int i = threadIdx.x; i < D; i += BLOCK)
-    atomicAdd(&dw_partial[i], dw_lds[i]);
+}
+
+// dw (and db) of the norm backwards outside the bf16 register path, in a
+// fixed order.  Those kernels used to add every block's dw into one fp32
+// row with atomicAdd, gridDim deep, so dw depended on the order the blocks
+// arrived in (measured on 2050 x 64 fp32: 2.8e-7 to 1.08e-5 relative from
+// run to run) and needed [D] (LayerNorm: [2D]) floats of dynamic LDS.  Here
+// a block owns DW_COLS columns; its DW_LANES row lanes each sum every
+// DW_LANES-th row in row order, and lane 0 adds the lane sums in lane
+// order.  MEAN == false is RMSNorm (xhat = x * rstd, no db).
+constexpr int DW_COLS = 16;
+constexpr int DW_LANES = BLOCK / DW_COLS;
+
+template <typename T, bool MEAN>
+__global__ void norm_bwd_dwdb_kernel(const T* __restrict__ dy,
+                                     const T* __restrict__ x,
+                                     const float* __restrict__ mean,
+                                     const float* __restrict__ rstd,
+                                     float* __restrict__ dw,
+                                     float* __restrict__ db,
+                                     int rows, int D) {
+  __shared__ float lds_w[DW_LANES][DW_COLS];
+  __shared__ float lds_b[DW_LANES][DW_COLS];
+  const int c = threadIdx.x % DW_COLS;
+  const int lane = threadIdx.x / DW_COLS;
+  const int col = blockIdx.x * DW_COLS + c;
+  float aw = 0.f, ab = 0.f;
+  if (col < D) {
+    for (int row = lane; row < rows; row += DW_LANES) {
+      const long off = (long)row * D;
+      float xv = load_as_f32(x + off, col);
+      float dyv = load_as_f32(dy + off, col);
+      float xhat = MEAN ? (xv - mean[row]) * rstd[row] : xv * rstd[row];
+      aw += dyv * xhat;
+      ab += dyv;
+    }
+  }
+  lds_w[lane][c] = aw;
+  lds_b[lane][c] = ab;
+  __syncthreads();
+  if (lane == 0 && col < D) {
+    float sw = 0.f, sb = 0.f;
+    for (int l = 0; l < DW_LANES; ++l) {
+      sw += lds_w[l][c];
+      sb += lds_b[l][c];
+    }
+    dw[col] = sw;
+    if (MEAN) db[col] = sb;
+  }
 }
 
 // -------------------------------------------------------------- LayerNorm
+
+// LayerNorm statistics.  The one-pass form var = ss/D - mu^2 has a relative
+// error of about (1 + mu^2/var) ulps: fine on centred rows, catastrophic once
+// |mean| >> std (measured: a 1000 + randn fp32 row got an rstd 11% off, a
+// 100 + 1e-3*randn row a negative variance and NaN).  So the one-pass
+// result is kept only while mu^2 <= var, where it is as good as any; every
+// other row (NaN included) takes a second pass: the sums of (x - mu0) and
+// (x - mu0)^2, the first of which also refines the mean.  The test is
+// uniform over the block.
+DEVINL bool ln_one_pass_ok(float mu, float var) { return mu * mu <= var; }
+
+DEVINL void ln_finish_stats(float mu0, float d1, float d2, int D, float eps,
+                            float& mu, float& r) {
+  const float c = d1 / D;
+  mu = mu0 + c;
+  const float var = fmaxf(d2 / D - c * c, 0.f);
+  r = rsqrtf(var + eps);
+}
 
 template <typename T>
 __global__ void layernorm_fwd_kernel(const T* __restrict__ x,
@@ -115,7 +173,7 @@ __global__ void layernorm_fwd_kernel(const T* __restrict__ x,
                                      float* __restrict__ mean,
                                      float* __restrict__ rstd,
                                      int rows, int D, float eps) {
-  __shared__ float lds[BLOCK / WAVE];
+  __shared__ float lds[3 * BLOCK / WAVE];
   for (int row = blockIdx.x; row < rows; row += gridDim.x) {
     const T* xr = x + (long)row * D;
     T* yr = y + (long)row * D;
@@ -131,6 +189,18 @@ __global__ void layernorm_fwd_kernel(const T* __restrict__ x,
     float mu = s / D;
     float var = ss / D - mu * mu;
     float r = rsqrtf(var + eps);
+    if (!ln_one_pass_ok(mu, var)) {
+      const float mu0 = mu;
+      float d1 = 0.f, d2 = 0.f;
+      for (int i = threadIdx.x; i < D; i += BLOCK) {
+        float d = load_as_f32(xr, i) - mu0;
+        d1 += d;
+        d2 += d * d;
+      }
+      d1 = block_sum<BLOCK>(d1, lds + BLOCK / WAVE);
+      d2 = block_sum<BLOCK>(d2, lds + 2 * BLOCK / WAVE);
+      ln_finish_stats(mu0, d1, d2, D, eps, mu, r);
+    }
     if (threadIdx.x == 0) { mean[row] = mu; rstd[row] = r; }
     for (int i = threadIdx.x; i < D; i += BLOCK) {
       float v = load_as_f32(xr, i);
@@ -149,16 +219,9 @@ __global__ void layernorm_bwd_kernel(const T* __restrict__ dy,
                                      const float* __restrict__ mean,
                                      const float* __restrict__ rstd,
                                      T* __restrict__ dx,
-                                     float* __restrict__ dw_partial,
-                                     float* __restrict__ db_partial,
                                      int rows, int D) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* dw_lds = (float*)smem;
-  float* db_lds = dw_lds + D;
-  float* scratch = db_lds + D;
-  for (int i = threadIdx.x; i < D; i += BLOCK) { dw_lds[i] = 0.f; db_lds[i] = 0.f; }
-  __syncthreads();
-
+  // dx only: dw and db come from norm_bwd_dwdb_kernel
+  __shared__ float scratch[BLOCK / WAVE];
   for (int row = blockIdx.x; row < rows; row += gridDim.x) {
     const T* dyr = dy + (long)row * D;
     const T* xr = x + (long)row * D;
@@ -181,14 +244,8 @@ __global__ void layernorm_bwd_kernel(const T* __restrict__ dy,
       float dyv = load_as_f32(dyr, i);
       float wdy = load_as_f32(w, i) * dyv;
       store_from_f32(dxr, i, r * (wdy - m1 - xhat * m2));
-      dw_lds[i] += dyv * xhat;
-      db_lds[i] += dyv;
     }
     __syncthreads();
-  }
-  for (int i = threadIdx.x; i < D; i += BLOCK) {
-    atomicAdd(&dw_partial[i], dw_lds[i]);
-    atomicAdd(&db_partial[i], db_lds[i]);
   }
 }
 
@@ -256,13 +313,9 @@ __global__ void rmsnorm_bwd_bf16v8(const unsigned short* __restrict__ dy,
                                    const unsigned short* __restrict__ w,
                                    const float* __restrict__ rstd,
                                    unsigned short* __restrict__ dx,
-                                   float* __restrict__ dw_partial,
                                    int rows, int D) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* dw_lds = (float*)smem;
-  float* scratch = dw_lds + D;
-  for (int i = threadIdx.x; i < D; i += BLOCK) dw_lds[i] = 0.f;
-  __syncthreads();
+  // dx only: dw comes from norm_bwd_dwdb_kernel
+  __shared__ float scratch[BLOCK / WAVE];
   for (int row = blockIdx.x; row < rows; row += gridDim.x) {
     const unsigned short* dyr = dy + (long)row * D;
     const unsigned short* xr = x + (long)row * D;
@@ -283,36 +336,46 @@ __global__ void rmsnorm_bwd_bf16v8(const unsigned short* __restrict__ dy,
       for (int j = 0; j < 8; ++j) {
         float xhat = xv.v[j] * r;
         out.v[j] = r * (wv.v[j] * dyv.v[j] - xhat * dot);
-        dw_lds[i + j] += dyv.v[j] * xhat;
       }
       store8f(dxr + i, out);
     }
     __syncthreads();
   }
-  for (int i = threadIdx.x; i < D; i += BLOCK)
-    atomicAdd(&dw_partial[i], dw_lds[i]);
 }
 
-__global__ void layernorm_fwd_bf16v8(const unsigned short* __restrict__ x,
-                                     const unsigned short* __restrict__ w,
-                                     const unsigned short* __restrict__ b,
-                                     unsigned short* __restrict__ y,
-                                     float* __restrict__ mean,
-                                     float* __restrict__ rstd,
-                                     int rows, int D, float eps) {
-  __shared__ float lds[2 * BLOCK / WAVE];
+// The row's chunks stay in registers (NC chunks of 8 per thread, as in the
+// *_reg backward kernels): x is read from memory once, and the second pass
+// of an off-centre row costs no memory traffic.
+template <int NC>
+__global__ void __launch_bounds__(BLOCK)
+layernorm_fwd_bf16v8(const unsigned short* __restrict__ x,
+                     const unsigned short* __restrict__ w,
+                     const unsigned short* __restrict__ b,
+                     unsigned short* __restrict__ y,
+                     float* __restrict__ mean,
+                     float* __restrict__ rstd,
+                     int rows, int D, float eps) {
+  __shared__ float lds[4 * BLOCK / WAVE];
+  const int wid = threadIdx.x / WAVE;
   for (int row = blockIdx.x; row < rows; row += gridDim.x) {
     const unsigned short* xr = x + (long)row * D;
     unsigned short* yr = y + (long)row * D;
+    f8 xv[NC];
     float s = 0.f, ss = 0.f;
-    for (int i = threadIdx.x * 8; i < D; i += BLOCK * 8) {
-      f8 v = load8f(xr + i);
 #pragma unroll
-      for (int j = 0; j < 8; ++j) { s += v.v[j]; ss += v.v[j] * v.v[j]; }
+    for (int c = 0; c < NC; ++c) {
+      int i = threadIdx.x * 8 + c * BLOCK * 8;
+      if (i < D) {
+        xv[c] = load8f(xr + i);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          s += xv[c].v[j];
+          ss += xv[c].v[j] * xv[c].v[j];
+        }
+      }
     }
-    // two block sums sharing one pass: use separate scratch halves
+    // two block sums behind one barrier: separate scratch quarters
     {
-      const int wid = threadIdx.x / WAVE;
       float sw = wave_sum(s), ssw = wave_sum(ss);
       if ((threadIdx.x & (WAVE - 1)) == 0) {
         lds[wid] = sw;
@@ -329,14 +392,47 @@ __global__ void layernorm_fwd_bf16v8(const unsigned short* __restrict__ x,
     float mu = s / D;
     float var = ss / D - mu * mu;
     float r = rsqrtf(var + eps);
-    if (threadIdx.x == 0) { mean[row] = mu; rstd[row] = r; }
-    for (int i = threadIdx.x * 8; i < D; i += BLOCK * 8) {
-      f8 v = load8f(xr + i), wv = load8f(w + i), bv = load8f(b + i);
-      f8 out;
+    if (!ln_one_pass_ok(mu, var)) {
+      const float mu0 = mu;
+      float d1 = 0.f, d2 = 0.f;
 #pragma unroll
-      for (int j = 0; j < 8; ++j)
-        out.v[j] = (v.v[j] - mu) * r * wv.v[j] + bv.v[j];
-      store8f(yr + i, out);
+      for (int c = 0; c < NC; ++c) {
+        int i = threadIdx.x * 8 + c * BLOCK * 8;
+        if (i < D) {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            float d = xv[c].v[j] - mu0;
+            d1 += d;
+            d2 += d * d;
+          }
+        }
+      }
+      float a = wave_sum(d1), q = wave_sum(d2);
+      if ((threadIdx.x & (WAVE - 1)) == 0) {
+        lds[2 * BLOCK / WAVE + wid] = a;
+        lds[3 * BLOCK / WAVE + wid] = q;
+      }
+      __syncthreads();
+      d1 = 0.f; d2 = 0.f;
+#pragma unroll
+      for (int i = 0; i < BLOCK / WAVE; ++i) {
+        d1 += lds[2 * BLOCK / WAVE + i];
+        d2 += lds[3 * BLOCK / WAVE + i];
+      }
+      ln_finish_stats(mu0, d1, d2, D, eps, mu, r);
+    }
+    if (threadIdx.x == 0) { mean[row] = mu; rstd[row] = r; }
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      int i = threadIdx.x * 8 + c * BLOCK * 8;
+      if (i < D) {
+        f8 wv = load8f(w + i), bv = load8f(b + i);
+        f8 out;
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+          out.v[j] = (xv[c].v[j] - mu) * r * wv.v[j] + bv.v[j];
+        store8f(yr + i, out);
+      }
     }
     __syncthreads();
   }
@@ -348,15 +444,9 @@ __global__ void layernorm_bwd_bf16v8(const unsigned short* __restrict__ dy,
                                      const float* __restrict__ mean,
                                      const float* __restrict__ rstd,
                                      unsigned short* __restrict__ dx,
-                                     float* __restrict__ dw_partial,
-                                     float* __restrict__ db_partial,
                                      int rows, int D) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* dw_lds = (float*)smem;
-  float* db_lds = dw_lds + D;
-  float* scratch = db_lds + D;   // 2*BLOCK/WAVE floats
-  for (int i = threadIdx.x; i < D; i += BLOCK) { dw_lds[i] = 0.f; db_lds[i] = 0.f; }
-  __syncthreads();
+  // dx only: dw and db come from norm_bwd_dwdb_kernel
+  __shared__ float scratch[2 * BLOCK / WAVE];
   for (int row = blockIdx.x; row < rows; row += gridDim.x) {
     const unsigned short* dyr = dy + (long)row * D;
     const unsigned short* xr = x + (long)row * D;
@@ -397,16 +487,10 @@ __global__ void layernorm_bwd_bf16v8(const unsigned short* __restrict__ dy,
       for (int j = 0; j < 8; ++j) {
         float xhat = (xv.v[j] - mu) * r;
         out.v[j] = r * (wv.v[j] * dyv.v[j] - m1 - xhat * m2);
-        dw_lds[i + j] += dyv.v[j] * xhat;
-        db_lds[i + j] += dyv.v[j];
       }
       store8f(dxr + i, out);
     }
     __syncthreads();
-  }
-  for (int i = threadIdx.x; i < D; i += BLOCK) {
-    atomicAdd(&dw_partial[i], dw_lds[i]);
-    atomicAdd(&db_partial[i], db_lds[i]);
   }
 }
 
@@ -604,13 +688,11 @@ std::vector<torch::Tensor> rmsnorm_bwd(torch::Tensor dy, torch::Tensor x,
   auto dx = torch::empty_like(x);
   auto stream = at::cuda::getCurrentHIPStream();
   dim3 grid(pick_grid(rows)), block(BLOCK);
-  size_t lds = (D + BLOCK / WAVE) * sizeof(float);
   const bool reg_path = x.scalar_type() == torch::kBFloat16 &&
       D % 8 == 0 && D <= 4 * BLOCK * 8;
-  auto dw_partial = reg_path
-      ? torch::empty({(long)grid.x, (long)D}, x.options().dtype(torch::kFloat))
-      : torch::zeros({D}, x.options().dtype(torch::kFloat));
   if (reg_path) {
+    auto dw_partial = torch::empty({(long)grid.x, (long)D},
+                                   x.options().dtype(torch::kFloat));
     int nc = (D + BLOCK * 8 - 1) / (BLOCK * 8);
 #define RMS_REG(NC)                                                          \
     hipLaunchKernelGGL(rmsnorm_bwd_bf16_reg<NC>, grid, block, 0, stream,     \
@@ -625,28 +707,43 @@ std::vector<torch::Tensor> rmsnorm_bwd(torch::Tensor dy, torch::Tensor x,
 #undef RMS_REG
     HIP_CHECK_LAST();
     return {dx, dw_partial.sum(0).to(w.scalar_type())};
-  } else if (x.scalar_type() == torch::kBFloat16 && D % 8 == 0) {
-    hipLaunchKernelGGL(rmsnorm_bwd_bf16v8, grid, block, lds, stream,
-                       (const unsigned short*)dy.data_ptr(),
-                       (const unsigned short*)x.data_ptr(),
-                       (const unsigned short*)w.data_ptr(),
-                       rstd.data_ptr<float>(), (unsigned short*)dx.data_ptr(),
-                       dw_partial.data_ptr<float>(), (int)rows, D);
-  } else if (x.scalar_type() == torch::kBFloat16) {
-    hipLaunchKernelGGL(rmsnorm_bwd_kernel<bf16_t>, grid, block, lds, stream,
-                       (const bf16_t*)dy.data_ptr(), (const bf16_t*)x.data_ptr(),
-                       (const bf16_t*)w.data_ptr(), rstd.data_ptr<float>(),
-                       (bf16_t*)dx.data_ptr(), dw_partial.data_ptr<float>(),
-                       (int)rows, D);
+  }
+  // dx from the row kernels, dw from the fixed-order column kernel
+  auto dw = torch::empty({D}, x.options().dtype(torch::kFloat));
+  dim3 grid_dw((D + DW_COLS - 1) / DW_COLS);
+  if (x.scalar_type() == torch::kBFloat16) {
+    if (D % 8 == 0) {
+      hipLaunchKernelGGL(rmsnorm_bwd_bf16v8, grid, block, 0, stream,
+                         (const unsigned short*)dy.data_ptr(),
+                         (const unsigned short*)x.data_ptr(),
+                         (const unsigned short*)w.data_ptr(),
+                         rstd.data_ptr<float>(),
+                         (unsigned short*)dx.data_ptr(), (int)rows, D);
+    } else {
+      hipLaunchKernelGGL(rmsnorm_bwd_kernel<bf16_t>, grid, block, 0, stream,
+                         (const bf16_t*)dy.data_ptr(),
+                         (const bf16_t*)x.data_ptr(),
+                         (const bf16_t*)w.data_ptr(), rstd.data_ptr<float>(),
+                         (bf16_t*)dx.data_ptr(), (int)rows, D);
+    }
+    hipLaunchKernelGGL((norm_bwd_dwdb_kernel<bf16_t, false>), grid_dw, block,
+                       0, stream, (const bf16_t*)dy.data_ptr(),
+                       (const bf16_t*)x.data_ptr(), (const float*)nullptr,
+                       rstd.data_ptr<float>(), dw.data_ptr<float>(),
+                       (float*)nullptr, (int)rows, D);
   } else {
-    hipLaunchKernelGGL(rmsnorm_bwd_kernel<float>, grid, block, lds, stream,
+    TORCH_CHECK(x.scalar_type() == torch::kFloat, "bf16/f32 only");
+    hipLaunchKernelGGL(rmsnorm_bwd_kernel<float>, grid, block, 0, stream,
                        dy.data_ptr<float>(), x.data_ptr<float>(),
                        w.data_ptr<float>(), rstd.data_ptr<float>(),
-                       dx.data_ptr<float>(), dw_partial.data_ptr<float>(),
-                       (int)rows, D);
+                       dx.data_ptr<float>(), (int)rows, D);
+    hipLaunchKernelGGL((norm_bwd_dwdb_kernel<float, false>), grid_dw, block,
+                       0, stream, dy.data_ptr<float>(), x.data_ptr<float>(),
+                       (const float*)nullptr, rstd.data_ptr<float>(),
+                       dw.data_ptr<float>(), (float*)nullptr, (int)rows, D);
   }
   HIP_CHECK_LAST();
-  return {dx, dw_partial.to(w.scalar_type())};
+  return {dx, dw.to(w.scalar_type())};
 }
 
 std::vector<torch::Tensor> layernorm_fwd(torch::Tensor x, torch::Tensor w,
@@ -661,13 +758,19 @@ std::vector<torch::Tensor> layernorm_fwd(torch::Tensor x, torch::Tensor w,
   auto stream = at::cuda::getCurrentHIPStream();
   dim3 grid(pick_grid(rows)), block(BLOCK);
   if (x.scalar_type() == torch::kBFloat16 && D % 8 == 0) {
-    hipLaunchKernelGGL(layernorm_fwd_bf16v8, grid, block, 0, stream,
-                       (const unsigned short*)x.data_ptr(),
-                       (const unsigned short*)w.data_ptr(),
-                       (const unsigned short*)b.data_ptr(),
-                       (unsigned short*)y.data_ptr(),
-                       mean.data_ptr<float>(), rstd.data_ptr<float>(),
-                       (int)rows, D, (float)eps);
+    // MAX_D = 8 chunks of BLOCK * 8
+    const int nc = (D + BLOCK * 8 - 1) / (BLOCK * 8);
+#define LN_FWD(NC)                                                           \
+    hipLaunchKernelGGL(layernorm_fwd_bf16v8<NC>, grid, block, 0, stream,     \
+                       (const unsigned short*)x.data_ptr(),                  \
+                       (const unsigned short*)w.data_ptr(),                  \
+                       (const unsigned short*)b.data_ptr(),                  \
+                       (unsigned short*)y.data_ptr(),                        \
+                       mean.data_ptr<float>(), rstd.data_ptr<float>(),       \
+                       (int)rows, D, (float)eps)
+    if (nc == 1) LN_FWD(1); else if (nc == 2) LN_FWD(2);
+    else if (nc <= 4) LN_FWD(4); else LN_FWD(8);
+#undef LN_FWD
   } else if (x.scalar_type() == torch::kBFloat16) {
     hipLaunchKernelGGL(layernorm_fwd_kernel<bf16_t>, grid, block, 0, stream,
                        (const bf16_t*)x.data_ptr(), (const bf16_t*)w.data_ptr(),
@@ -694,16 +797,13 @@ std::vector<torch::Tensor> layernorm_bwd(torch::Tensor dy, torch::Tensor x,
   auto dx = torch::empty_like(x);
   auto stream = at::cuda::getCurrentHIPStream();
   dim3 grid(pick_grid(rows)), block(BLOCK);
-  size_t lds = (2 * D + 2 * (BLOCK / WAVE)) * sizeof(float);
   const bool reg_path = x.scalar_type() == torch::kBFloat16 &&
       D % 8 == 0 && D <= 4 * BLOCK * 8;
-  auto dw_partial = reg_path
-      ? torch::empty({(long)grid.x, (long)D}, x.options().dtype(torch::kFloat))
-      : torch::zeros({D}, x.options().dtype(torch::kFloat));
-  auto db_partial = reg_path
-      ? torch::empty({(long)grid.x, (long)D}, x.options().dtype(torch::kFloat))
-      : torch::zeros({D}, x.options().dtype(torch::kFloat));
   if (reg_path) {
+    auto dw_partial = torch::empty({(long)grid.x, (long)D},
+                                   x.options().dtype(torch::kFloat));
+    auto db_partial = torch::empty({(long)grid.x, (long)D},
+                                   x.options().dtype(torch::kFloat));
     int nc = (D + BLOCK * 8 - 1) / (BLOCK * 8);
 #define LN_REG(NC)                                                           \
     hipLaunchKernelGGL(layernorm_bwd_bf16_reg<NC>, grid, block, 0, stream,   \
@@ -720,30 +820,45 @@ std::vector<torch::Tensor> layernorm_bwd(torch::Tensor dy, torch::Tensor x,
     HIP_CHECK_LAST();
     return {dx, dw_partial.sum(0).to(w.scalar_type()),
             db_partial.sum(0).to(w.scalar_type())};
-  } else if (x.scalar_type() == torch::kBFloat16 && D % 8 == 0) {
-    hipLaunchKernelGGL(layernorm_bwd_bf16v8, grid, block, lds, stream,
-                       (const unsigned short*)dy.data_ptr(),
-                       (const unsigned short*)x.data_ptr(),
-                       (const unsigned short*)w.data_ptr(),
-                       mean.data_ptr<float>(), rstd.data_ptr<float>(),
-                       (unsigned short*)dx.data_ptr(),
-                       dw_partial.data_ptr<float>(),
-                       db_partial.data_ptr<float>(), (int)rows, D);
-  } else if (x.scalar_type() == torch::kBFloat16) {
-    hipLaunchKernelGGL(layernorm_bwd_kernel<bf16_t>, grid, block, lds, stream,
-                       (const bf16_t*)dy.data_ptr(), (const bf16_t*)x.data_ptr(),
-                       (const bf16_t*)w.data_ptr(), mean.data_ptr<float>(),
-                       rstd.data_ptr<float>(), (bf16_t*)dx.data_ptr(),
-                       dw_partial.data_ptr<float>(), db_partial.data_ptr<float>(),
-                       (int)rows, D);
+  }
+  // dx from the row kernels, dw and db from the fixed-order column kernel
+  auto dw = torch::empty({D}, x.options().dtype(torch::kFloat));
+  auto db = torch::empty({D}, x.options().dtype(torch::kFloat));
+  dim3 grid_dw((D + DW_COLS - 1) / DW_COLS);
+  if (x.scalar_type() == torch::kBFloat16) {
+    if (D % 8 == 0) {
+      hipLaunchKernelGGL(layernorm_bwd_bf16v8, grid, block, 0, stream,
+                         (const unsigned short*)dy.data_ptr(),
+                         (const unsigned short*)x.data_ptr(),
+                         (const unsigned short*)w.data_ptr(),
+                         mean.data_ptr<float>(), rstd.data_ptr<float>(),
+                         (unsigned short*)dx.data_ptr(), (int)rows, D);
+    } else {
+      hipLaunchKernelGGL(layernorm_bwd_kernel<bf16_t>, grid, block, 0, stream,
+                         (const bf16_t*)dy.data_ptr(),
+                         (const bf16_t*)x.data_ptr(),
+                         (const bf16_t*)w.data_ptr(), mean.data_ptr<float>(),
+                         rstd.data_ptr<float>(), (bf16_t*)dx.data_ptr(),
+                         (int)rows, D);
+    }
+    hipLaunchKernelGGL((norm_bwd_dwdb_kernel<bf16_t, true>), grid_dw, block,
+                       0, stream, (const bf16_t*)dy.data_ptr(),
+                       (const bf16_t*)x.data_ptr(), mean.data_ptr<float>(),
+                       rstd.data_ptr<float>(), dw.data_ptr<float>(),
+                       db.data_ptr<float>(), (int)rows, D);
   } else {
-    hipLaunchKernelGGL(layernorm_bwd_kernel<float>, grid, block, lds, stream,
+    TORCH_CHECK(x.scalar_type() == torch::kFloat, "bf16/f32 only");
+    hipLaunchKernelGGL(layernorm_bwd_kernel<float>, grid, block, 0, stream,
                        dy.data_ptr<float>(), x.data_ptr<float>(),
                        w.data_ptr<float>(), mean.data_ptr<float>(),
                        rstd.data_ptr<float>(), dx.data_ptr<float>(),
-                       dw_partial.data_ptr<float>(), db_partial.data_ptr<float>(),
+                       (int)rows, D);
+    hipLaunchKernelGGL((norm_bwd_dwdb_kernel<float, true>), grid_dw, block,
+                       0, stream, dy.data_ptr<float>(), x.data_ptr<float>(),
+                       mean.data_ptr<float>(), rstd.data_ptr<float>(),
+                       dw.data_ptr<float>(), db.data_ptr<float>(),
                        (int)rows, D);
   }
   HIP_CHECK_LAST();
-  return {dx, dw_partial.to(w.scalar_type()), db_partial.to(w.scalar_type())};
+  return {dx, dw.to(w.scalar_type()), db.to(w.scalar_type())};
 }
