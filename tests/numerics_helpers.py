@@ -389,3 +389,219 @@ def attn_dq_cancel_scale(q, k, v, do, causal, scale):
 
 def attn_lse(q, k, causal, scale):
     return torch.logsumexp(_attn_scores(q, k, causal, scale), -1)
+
+
+# --------------------------------------------------------------- optimizer
+#
+# One AdamW step is judged element by element, each output against the size
+# of the terms that can cancel in it (the idea of ``attn_dq_cancel_scale``):
+#   e_m = max |m' - ref| / (|b1*m| + |(1-b1)*g| + TINY)
+#   e_v = max |v' - ref| / (ref + TINY)
+#   e_p = max |p' - ref| / (|p*(1-lr*wd)|
+#                           + lr/bc1 * (|b1*m| + |(1-b1)*g|)
+#                             / (sqrt(v'_ref/bc2) + eps) + TINY)
+# and held to e(kernel) <= max(2.5 * e(lib), FLOOR_OPT) where lib is
+# torch.optim.AdamW(foreach=False) in fp32 on the same device.
+# FLOOR_OPT = 2**-21 is 4 fp32 ulp (ulp = 2**-23): m' = b1*m + (1-b1)*g
+# rounds two products and one sum (3 roundings of at most half an ulp of the
+# terms), the coefficients b1 / 1-b1 are each rounded once (half an ulp of
+# their term), and v' and p' repeat the pattern with one more division and
+# square root; 4 ulp covers the recurrence plus the coefficient rounding
+# without leaving room for a coefficient formed in fp32 (1.f - 0.999f is
+# 1.3e-5 off, 27 times the floor).
+
+OPT_FAMILIES = ["randn", "small_p", "eps_scale", "tiny_grad", "big_grad",
+                "wide", "zero_grad"]
+OPT_STEPS = [1, 2, 10, 1000]
+OPT_BETAS = [(0.9, 0.95), (0.9, 0.999)]
+OPT_HYPER = dict(lr=1e-3, eps=1e-8, weight_decay=0.1)
+FLOOR_OPT = 2.0 ** -21
+
+
+def opt_input(family, n, step, betas, dtype=torch.float32):
+    """fp32 CPU (p, g, m, v) entering AdamW step ``step``.  ``dtype`` bf16
+    rounds p and g to bf16 (m and v are fp32 state whatever the params are).
+
+    The moments are the stationary ones for iid gradients of scale s after
+    step-1 steps: m = randn*s*sqrt((1-b1)/(1+b1))*(1-b1^(t-1)),
+    v = s^2*(1-b2^(t-1))*U(0.5, 1.5); both 0 for step 1."""
+    gen = _gen("opt", family, n, step, betas, dtype)
+    b1, b2 = betas
+    p = _randn((n,), gen)
+    r = _randn((n,), gen)
+    s = torch.ones(n, dtype=torch.float64)        # gradient scale
+    if family == "randn":
+        g = r
+    elif family == "small_p":                     # the update dominates
+        p = 1e-4 * p
+        g = r
+    elif family == "eps_scale":                   # sqrt(v) ~ eps
+        s = s * 1e-8
+        g = r * s
+    elif family == "tiny_grad":
+        s = s * 1e-12
+        g = r * s
+    elif family == "big_grad":
+        s = s * 1e12
+        g = r * s
+    elif family == "wide":                        # |g| log-uniform 1e-10..1e6
+        u = torch.rand(n, generator=gen, dtype=torch.float64)
+        s = 10.0 ** (u * 16.0 - 10.0)
+        g = torch.sign(r) * s
+    elif family == "zero_grad":                   # pure decay, never NaN
+        g = torch.zeros(n, dtype=torch.float64)
+    else:
+        raise KeyError(family)
+    t = step - 1
+    m = _randn((n,), gen) * s * math.sqrt((1 - b1) / (1 + b1)) * (1 - b1 ** t)
+    v = s * s * (1 - b2 ** t) * \
+        (0.5 + torch.rand(n, generator=gen, dtype=torch.float64))
+    if family == "zero_grad":
+        m[::2] = 0.0
+        v[::2] = 0.0
+    p, g = p.to(dtype).float(), g.to(dtype).float()
+    return p, g, m.float(), v.float()
+
+
+def adamw_ref(p, g, m, v, step, lr, betas, eps, weight_decay):
+    """One AdamW step in fp64 with the user's double hyper-parameters.
+    Returns (p', m', v')."""
+    p, g, m, v = (t.detach().double().cpu() for t in (p, g, m, v))
+    b1, b2 = betas
+    m2 = b1 * m + (1 - b1) * g
+    v2 = b2 * v + (1 - b2) * g * g
+    bc1 = 1 - b1 ** step
+    bc2 = 1 - b2 ** step
+    p2 = p * (1 - lr * weight_decay) \
+        - lr / bc1 * m2 / ((v2 / bc2).sqrt() + eps)
+    return p2, m2, v2
+
+
+def adamw_lib(p, g, m, v, step, lr, betas, eps, weight_decay, device="cpu"):
+    """The same step by torch.optim.AdamW(foreach=False) in fp32 on
+    ``device``, its state preloaded with step-1, m and v."""
+    pp = torch.nn.Parameter(p.detach().float().to(device).clone())
+    pp.grad = g.detach().float().to(device).clone()
+    opt = torch.optim.AdamW([pp], lr=lr, betas=betas, eps=eps,
+                            weight_decay=weight_decay, foreach=False)
+    opt.state[pp] = {"step": torch.tensor(float(step - 1)),
+                     "exp_avg": m.detach().float().to(device).clone(),
+                     "exp_avg_sq": v.detach().float().to(device).clone()}
+    opt.step()
+    st = opt.state[pp]
+    assert int(st["step"]) == step
+    return pp.detach(), st["exp_avg"], st["exp_avg_sq"]
+
+
+def optim_err(got, ins, step, lr, betas, eps, weight_decay, keep=None):
+    """{"p","m","v"} -> element-wise error of got = (p', m', v') against
+    ``adamw_ref`` of ins = (p, g, m, v), in the units described above.
+    ``keep`` (bool mask) restricts the maximum to those elements."""
+    p, g, m, v = (t.detach().double().cpu() for t in ins)
+    gp, gm, gv = (t.detach().double().cpu() for t in got)
+    rp, rm, rv = adamw_ref(p, g, m, v, step, lr, betas, eps, weight_decay)
+    b1, b2 = betas
+    bc1 = 1 - b1 ** step
+    bc2 = 1 - b2 ** step
+    mterms = (b1 * m).abs() + ((1 - b1) * g).abs()
+    e = {
+        "m": (gm - rm).abs() / (mterms + TINY),
+        "v": (gv - rv).abs() / (rv + TINY),
+        "p": (gp - rp).abs() / ((p * (1 - lr * weight_decay)).abs()
+                                + lr / bc1 * mterms
+                                / ((rv / bc2).sqrt() + eps) + TINY),
+    }
+    out = {}
+    for k, t in e.items():
+        if keep is not None:
+            t = t[keep]
+        assert not torch.isnan(t).any(), f"{k}: NaN in a result"
+        out[k] = t.max().item() if t.numel() else 0.0
+    return out
+
+
+def optim_check(got, ins, step, hyper, betas, device, what, keep=None,
+                floor=FLOOR_OPT, lib=None):
+    """Assert e(got) <= max(2.5 * e(lib), floor) for p', m' and v'.
+    Returns (e_got, e_lib) dicts."""
+    if lib is None:
+        lib = adamw_lib(*ins, step, hyper["lr"], betas, hyper["eps"],
+                        hyper["weight_decay"], device=device)
+    args = (step, hyper["lr"], betas, hyper["eps"], hyper["weight_decay"])
+    e_got = optim_err(got, ins, *args, keep=keep)
+    e_lib = optim_err(lib, ins, *args, keep=keep)
+    bad = []
+    for k in ("p", "m", "v"):
+        bound = max(MARGIN * e_lib[k], floor)
+        print(f"NUMERICS {what} {k}: e_got={e_got[k]:.3e} "
+              f"e_lib={e_lib[k]:.3e} bound={bound:.3e}")
+        if not e_got[k] <= bound:
+            bad.append(f"{k}: e(got)={e_got[k]:.3e} > max({MARGIN}*"
+                       f"e(lib)={e_lib[k]:.3e}, floor={floor:.3e})")
+    assert not bad, f"{what}: " + "; ".join(bad)
+    return e_got, e_lib
+
+
+def adamw_emulate(p, g, m, v, step, lr, betas, eps, weight_decay,
+                  coef="double", eps_inside=False):
+    """The HIP kernels' arithmetic in fp32 torch ops on the CPU (no fused
+    multiply-add).  coef="double": 1-b1, 1-b2, bc2, lr/bc1 and 1-lr*wd formed
+    in double and rounded once, as the kernels do.  coef="fp32": formed in
+    fp32 from the rounded betas, as they once did.  ``eps_inside`` puts eps
+    under the square root (a wrong kernel, for the teeth check)."""
+    f32 = torch.float32
+    p, g, m, v = (t.detach().to(f32).clone() for t in (p, g, m, v))
+    b1, b2 = betas
+    T = lambda x: torch.tensor(x, dtype=f32)
+    b1f, b2f, epsf = T(b1), T(b2), T(eps)
+    if coef == "double":
+        omb1, omb2 = T(1 - b1), T(1 - b2)
+        bc2 = T(1 - b2 ** step)
+        step_size = T(lr / (1 - b1 ** step))
+        decay = T(1 - lr * weight_decay)
+    else:
+        assert coef == "fp32"
+        one = T(1.0)
+        omb1, omb2 = one - b1f, one - b2f
+        bc1 = one - torch.pow(b1f, T(float(step)))
+        bc2 = one - torch.pow(b2f, T(float(step)))
+        step_size = T(lr) / bc1
+        decay = one - T(lr) * T(weight_decay)
+    m2 = m * b1f + g * omb1
+    v2 = v * b2f + g * g * omb2
+    if eps_inside:
+        den = torch.sqrt(v2 / bc2 + epsf)
+    else:
+        den = torch.sqrt(v2 / bc2) + epsf
+    p2 = p * decay - step_size * m2 / den
+    return p2, m2, v2
+
+
+# --------------------------------------------------------------------- EMA
+#
+# ema' = d*ema + (1-d)*p, each element against the terms that add up to it:
+#   e = max |ema' - ref| / (|d*ema| + |(1-d)*p| + TINY)
+# FLOOR_EMA = 2**-22 (2 fp32 ulp): d and 1-d are each rounded once (half an
+# ulp of their term), the two products and the sum round once each.
+
+FLOOR_EMA = 2.0 ** -22
+
+
+def ema_err(got, ema, p, decay):
+    ema, p = ema.detach().double().cpu(), p.detach().double().cpu()
+    ref = decay * ema + (1 - decay) * p
+    e = (got.detach().double().cpu() - ref).abs() / \
+        ((decay * ema).abs() + ((1 - decay) * p).abs() + TINY)
+    assert not torch.isnan(e).any()
+    return e.max().item()
+
+
+# --------------------------------------------------------------- l2norm_sq
+#
+# A sum of n non-negative terms: every rounding is relative to a partial sum
+# that is at most the result, so the relative error is at most (number of
+# roundings on the longest chain) * 2**-24.  The kernel's chain for the
+# largest size tested (2048*256+13) is 1 (square) + 2 (per-thread serial)
+# + 6 + 4 (wave, block) + 8 (per-thread partials) + 6 + 4 = 31 <= 64.
+
+FLOOR_L2NORM = 64 * 2.0 ** -24

@@ -365,7 +365,8 @@ def fused_adamw_(param: torch.Tensor, grad: torch.Tensor,
 def ema_update_(ema: torch.Tensor, param: torch.Tensor, decay: float):
     """ema = decay*ema + (1-decay)*param, fused."""
     if ema.is_cuda:
-        ext("ema_update").ema_update(ema, param, decay)
+        # the kernel reads param as ema.numel() dense elements
+        ext("ema_update").ema_update(ema, param.contiguous(), decay)
         return
     ema.lerp_(param.to(ema.dtype), 1.0 - decay)
 

@@ -23,6 +23,17 @@ void multi_adamw_step(torch::Tensor cpid, torch::Tensor coff,
                       torch::Tensor m, torch::Tensor v,
                       long step, double lr, double beta1, double beta2,
                       double eps, double wd, bool param_bf16, bool grad_bf16);
+void adamw_step_dev(torch::Tensor p, torch::Tensor g, torch::Tensor m,
+                    torch::Tensor v, torch::Tensor coef, double beta1,
+                    double beta2, double eps);
+void adamw_prelude(torch::Tensor step, torch::Tensor hyp, torch::Tensor coef);
+void multi_adamw_step_dev(torch::Tensor cpid, torch::Tensor coff,
+                          torch::Tensor pptrs, torch::Tensor gptrs,
+                          torch::Tensor mptrs, torch::Tensor moffs,
+                          torch::Tensor numels,
+                          torch::Tensor m, torch::Tensor v,
+                          torch::Tensor coef, double beta1, double beta2,
+                          double eps, bool param_bf16, bool grad_bf16);
 void ema_update(torch::Tensor ema, torch::Tensor p, double decay);
 torch::Tensor l2norm_sq(torch::Tensor x);
 void scale_inplace(torch::Tensor x, double s);
@@ -74,6 +85,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bias_gelu_bwd", &bias_gelu_bwd);
   m.def("adamw_step", &adamw_step);
   m.def("multi_adamw_step", &multi_adamw_step);
+  m.def("adamw_step_dev", &adamw_step_dev);
+  m.def("adamw_prelude", &adamw_prelude);
+  m.def("multi_adamw_step_dev", &multi_adamw_step_dev);
   m.def("ema_update", &ema_update);
   m.def("l2norm_sq", &l2norm_sq);
   m.def("scale_inplace", &scale_inplace);

@@ -134,20 +134,79 @@ __global__ void bias_gelu_bwd_f32(const float* __restrict__ dy,
 
 // -------- fused AdamW on flat fp32 tensors -------------------------------
 
+// The step-dependent coefficients, each computed in double and rounded to
+// fp32 ONCE (forming 1.f - beta2 in fp32 with beta2 = 0.999 is 1.3e-5 off).
+// They come either from the host (adam_coef_host) or from device memory,
+// written by adam_prelude_kernel (the hipGraph-capturable optimizer).
+struct AdamCoef {
+  float omb1;       // 1 - beta1
+  float omb2;       // 1 - beta2
+  float bc2;        // 1 - beta2^step
+  float step_size;  // lr / (1 - beta1^step)
+  float decay;      // 1 - lr * wd
+};
+constexpr int ADAM_NCOEF = 5;   // floats per group in the device table
+constexpr int ADAM_NHYP = 4;    // doubles per group: lr, beta1, beta2, wd
+
+DEVINL AdamCoef adam_coef_load(AdamCoef c, const float* __restrict__ cdev) {
+  if (cdev != nullptr) {
+    c.omb1 = cdev[0];
+    c.omb2 = cdev[1];
+    c.bc2 = cdev[2];
+    c.step_size = cdev[3];
+    c.decay = cdev[4];
+  }
+  return c;
+}
+
+DEVINL void adam_elem(float& p, float& m, float& v, float g, float beta1,
+                      float beta2, float eps, const AdamCoef& c) {
+  float mi = m * beta1 + g * c.omb1;
+  float vi = v * beta2 + g * g * c.omb2;
+  m = mi;
+  v = vi;
+  p = p * c.decay - c.step_size * mi / (sqrtf(vi / c.bc2) + eps);
+}
+
+// One block: advances the device step counter and writes every group's
+// coefficients for the update kernels launched after it on the same stream.
+// Being a kernel, it is recorded by a hipGraph capture and runs again on
+// every replay, so the bias corrections follow the real step count.
+__global__ void adam_prelude_kernel(long* __restrict__ step,
+                                    const double* __restrict__ hyp,
+                                    float* __restrict__ coef, int ngroups) {
+  const long t = *step + 1;
+  __syncthreads();                 // every thread has read the old count
+  for (int g = threadIdx.x; g < ngroups; g += blockDim.x) {
+    const double lr = hyp[g * ADAM_NHYP + 0];
+    const double b1 = hyp[g * ADAM_NHYP + 1];
+    const double b2 = hyp[g * ADAM_NHYP + 2];
+    const double wd = hyp[g * ADAM_NHYP + 3];
+    const double bc1 = 1.0 - pow(b1, (double)t);
+    const double bc2 = 1.0 - pow(b2, (double)t);
+    float* c = coef + g * ADAM_NCOEF;
+    c[0] = (float)(1.0 - b1);
+    c[1] = (float)(1.0 - b2);
+    c[2] = (float)bc2;
+    c[3] = (float)(lr / bc1);
+    c[4] = (float)(1.0 - lr * wd);
+  }
+  if (threadIdx.x == 0) *step = t;
+}
+
 __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
                              float* __restrict__ m, float* __restrict__ v,
-                             long n, float lr, float beta1, float beta2,
-                             float eps, float wd, float bc1, float bc2) {
+                             long n, float beta1, float beta2, float eps,
+                             AdamCoef ch, const float* __restrict__ cdev) {
+  const AdamCoef c = adam_coef_load(ch, cdev);
   long i0 = (long)blockIdx.x * BLOCK + threadIdx.x;
   long stride = (long)gridDim.x * BLOCK;
   for (long i = i0; i < n; i += stride) {
-    float gi = g[i];
-    float pi = p[i] * (1.f - lr * wd);
-    float mi = m[i] * beta1 + gi * (1.f - beta1);
-    float vi = v[i] * beta2 + gi * gi * (1.f - beta2);
+    float pi = p[i], mi = m[i], vi = v[i];
+    adam_elem(pi, mi, vi, g[i], beta1, beta2, eps, c);
     m[i] = mi;
     v[i] = vi;
-    p[i] = pi - lr / bc1 * mi / (sqrtf(vi / bc2) + eps);
+    p[i] = pi;
   }
 }
 
@@ -156,28 +215,31 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
 // vectorized 4-wide (the v10 adamw lesson: scalar dword accesses cap the
 // HBM-bound kernels well below the roofline); scalar tail for n % 4
 __global__ void ema_kernel(float* __restrict__ ema, const float* __restrict__ p,
-                           long n, float decay, int vec4) {
+                           long n, float decay, float omd, int vec4) {
   const long n4 = vec4 ? (n >> 2) : 0;
   long i0 = (long)blockIdx.x * BLOCK + threadIdx.x;
   long stride = (long)gridDim.x * BLOCK;
   for (long i = i0; i < n4; i += stride) {
     float4 e = *(const float4*)(ema + i * 4);
     float4 v = *(const float4*)(p + i * 4);
-    e.x = decay * e.x + (1.f - decay) * v.x;
-    e.y = decay * e.y + (1.f - decay) * v.y;
-    e.z = decay * e.z + (1.f - decay) * v.z;
-    e.w = decay * e.w + (1.f - decay) * v.w;
+    e.x = decay * e.x + omd * v.x;
+    e.y = decay * e.y + omd * v.y;
+    e.z = decay * e.z + omd * v.z;
+    e.w = decay * e.w + omd * v.w;
     *(float4*)(ema + i * 4) = e;
   }
   for (long i = n4 * 4 + i0; i < n; i += stride)
-    ema[i] = decay * ema[i] + (1.f - decay) * p[i];
+    ema[i] = decay * ema[i] + omd * p[i];
 }
 
 // -------- l2 norm squared (any dtype -> f32 scalar) ----------------------
 
+// Each block writes its partial; l2norm_final_kernel adds them in a fixed
+// order.  (A float atomicAdd per block summed them in arrival order, so the
+// result, and with it the clip coefficient, changed from call to call.)
 template <typename T>
-__global__ void l2norm_kernel(const T* __restrict__ x, float* __restrict__ out,
-                              long n) {
+__global__ void l2norm_kernel(const T* __restrict__ x,
+                              float* __restrict__ partial, long n) {
   __shared__ float lds[BLOCK / WAVE];
   long i0 = (long)blockIdx.x * BLOCK + threadIdx.x;
   long stride = (long)gridDim.x * BLOCK;
@@ -189,7 +251,16 @@ __global__ void l2norm_kernel(const T* __restrict__ x, float* __restrict__ out,
     acc += v * v;
   }
   acc = block_sum<BLOCK>(acc, lds);
-  if (threadIdx.x == 0) atomicAdd(out, acc);
+  if (threadIdx.x == 0) partial[blockIdx.x] = acc;
+}
+
+__global__ void l2norm_final_kernel(const float* __restrict__ partial,
+                                    float* __restrict__ out, int nparts) {
+  __shared__ float lds[BLOCK / WAVE];
+  float acc = 0.f;
+  for (int i = threadIdx.x; i < nparts; i += BLOCK) acc += partial[i];
+  acc = block_sum<BLOCK>(acc, lds);
+  if (threadIdx.x == 0) *out = acc;
 }
 
 template <typename T>
@@ -209,6 +280,44 @@ __global__ void scale_kernel(T* __restrict__ x, long n, float s) {
 int ew_grid(long n, int per_thread = 1) {
   long blocks = (n + (long)BLOCK * per_thread - 1) / ((long)BLOCK * per_thread);
   return (int)(blocks > 2048 ? 2048 : (blocks > 0 ? blocks : 1));
+}
+
+AdamCoef adam_coef_host(long step, double lr, double beta1, double beta2,
+                        double wd) {
+  const double bc1 = 1.0 - std::pow(beta1, (double)step);
+  const double bc2 = 1.0 - std::pow(beta2, (double)step);
+  AdamCoef c;
+  c.omb1 = (float)(1.0 - beta1);
+  c.omb2 = (float)(1.0 - beta2);
+  c.bc2 = (float)bc2;
+  c.step_size = (float)(lr / bc1);
+  c.decay = (float)(1.0 - lr * wd);
+  return c;
+}
+
+// the flat kernel indexes all four tensors 0..p.numel() as dense fp32
+void check_adamw_flat(const torch::Tensor& p, const torch::Tensor& g,
+                      const torch::Tensor& m, const torch::Tensor& v) {
+  const torch::Tensor* ts[4] = {&p, &g, &m, &v};
+  const char* names[4] = {"p", "g", "m", "v"};
+  for (int i = 0; i < 4; ++i) {
+    TORCH_CHECK(ts[i]->is_cuda() && ts[i]->scalar_type() == torch::kFloat,
+                "adamw_step: ", names[i], " must be an fp32 device tensor");
+    TORCH_CHECK(ts[i]->is_contiguous(), "adamw_step: ", names[i],
+                " must be contiguous");
+    TORCH_CHECK(ts[i]->numel() == p.numel(), "adamw_step: ", names[i],
+                " has ", ts[i]->numel(), " elements, p has ", p.numel());
+    TORCH_CHECK(ts[i]->get_device() == p.get_device(), "adamw_step: ",
+                names[i], " is on another device than p");
+  }
+}
+
+void check_adam_coef(const torch::Tensor& coef, const torch::Tensor& like) {
+  TORCH_CHECK(coef.is_cuda() && coef.scalar_type() == torch::kFloat &&
+              coef.is_contiguous() && coef.numel() == ADAM_NCOEF &&
+              coef.get_device() == like.get_device(),
+              "adamw: coef must be ", ADAM_NCOEF,
+              " contiguous fp32 values on the params' device");
 }
 
 }  // namespace
@@ -264,24 +373,61 @@ torch::Tensor bias_gelu_bwd(torch::Tensor dy, torch::Tensor x,
 void adamw_step(torch::Tensor p, torch::Tensor g, torch::Tensor m,
                 torch::Tensor v, long step, double lr, double beta1,
                 double beta2, double eps, double wd) {
-  TORCH_CHECK(p.is_cuda() && p.scalar_type() == torch::kFloat);
-  TORCH_CHECK(p.is_contiguous() && g.is_contiguous());
+  check_adamw_flat(p, g, m, v);
   long n = p.numel();
-  float bc1 = 1.f - powf((float)beta1, (float)step);
-  float bc2 = 1.f - powf((float)beta2, (float)step);
   auto stream = at::cuda::getCurrentHIPStream();
   hipLaunchKernelGGL(adamw_kernel, dim3(ew_grid(n)), dim3(BLOCK), 0, stream,
                      p.data_ptr<float>(), g.data_ptr<float>(),
                      m.data_ptr<float>(), v.data_ptr<float>(), n,
-                     (float)lr, (float)beta1, (float)beta2, (float)eps,
-                     (float)wd, bc1, bc2);
+                     (float)beta1, (float)beta2, (float)eps,
+                     adam_coef_host(step, lr, beta1, beta2, wd),
+                     (const float*)nullptr);
+  HIP_CHECK_LAST();
+}
+
+// Same update with the coefficients read from ``coef`` (ADAM_NCOEF floats of
+// one group, written by adamw_prelude on the same stream).
+void adamw_step_dev(torch::Tensor p, torch::Tensor g, torch::Tensor m,
+                    torch::Tensor v, torch::Tensor coef, double beta1,
+                    double beta2, double eps) {
+  check_adamw_flat(p, g, m, v);
+  check_adam_coef(coef, p);
+  long n = p.numel();
+  auto stream = at::cuda::getCurrentHIPStream();
+  hipLaunchKernelGGL(adamw_kernel, dim3(ew_grid(n)), dim3(BLOCK), 0, stream,
+                     p.data_ptr<float>(), g.data_ptr<float>(),
+                     m.data_ptr<float>(), v.data_ptr<float>(), n,
+                     (float)beta1, (float)beta2, (float)eps, AdamCoef{},
+                     (const float*)coef.data_ptr<float>());
+  HIP_CHECK_LAST();
+}
+
+// step (int64[1]) += 1; coef[g] = coefficients of group g at the new step
+// from hyp[g] = (lr, beta1, beta2, wd) in double.  All three on the device.
+void adamw_prelude(torch::Tensor step, torch::Tensor hyp, torch::Tensor coef) {
+  TORCH_CHECK(step.is_cuda() && step.scalar_type() == torch::kLong &&
+              step.numel() == 1, "adamw_prelude: step must be a device int64");
+  TORCH_CHECK(hyp.is_cuda() && hyp.scalar_type() == torch::kDouble &&
+              hyp.is_contiguous() && hyp.dim() == 2 &&
+              hyp.size(1) == ADAM_NHYP,
+              "adamw_prelude: hyp must be a contiguous device double (G, 4)");
+  TORCH_CHECK(coef.is_cuda() && coef.scalar_type() == torch::kFloat &&
+              coef.is_contiguous() && coef.dim() == 2 &&
+              coef.size(0) == hyp.size(0) && coef.size(1) == ADAM_NCOEF,
+              "adamw_prelude: coef must be a contiguous device float (G, 5)");
+  TORCH_CHECK(step.get_device() == hyp.get_device() &&
+              step.get_device() == coef.get_device());
+  auto stream = at::cuda::getCurrentHIPStream();
+  hipLaunchKernelGGL(adam_prelude_kernel, dim3(1), dim3(WAVE), 0, stream,
+                     (long*)step.data_ptr<int64_t>(), hyp.data_ptr<double>(),
+                     coef.data_ptr<float>(), (int)hyp.size(0));
   HIP_CHECK_LAST();
 }
 
 namespace {
 __global__ void ema_bf16_kernel(float* __restrict__ ema,
                                 const unsigned short* __restrict__ p, long n,
-                                float decay, int vec4) {
+                                float decay, float omd, int vec4) {
   // GRID-STRIDED: ew_grid caps launches at 2048 blocks — a plain
   // one-element-per-thread body here updated only the first 524k elements
   // of an 8B-param shard (caught by the large-n parity test); 4-wide
@@ -293,20 +439,33 @@ __global__ void ema_bf16_kernel(float* __restrict__ ema,
   for (long i = i0; i < n4; i += stride) {
     float4 e = *(const float4*)(ema + i * 4);
     ushort4 v = *(const ushort4*)(p + i * 4);
-    e.x = decay * e.x + (1.f - decay) * bf2f(v.x);
-    e.y = decay * e.y + (1.f - decay) * bf2f(v.y);
-    e.z = decay * e.z + (1.f - decay) * bf2f(v.z);
-    e.w = decay * e.w + (1.f - decay) * bf2f(v.w);
+    e.x = decay * e.x + omd * bf2f(v.x);
+    e.y = decay * e.y + omd * bf2f(v.y);
+    e.z = decay * e.z + omd * bf2f(v.z);
+    e.w = decay * e.w + omd * bf2f(v.w);
     *(float4*)(ema + i * 4) = e;
   }
   for (long i = n4 * 4 + i0; i < n; i += stride)
-    ema[i] = decay * ema[i] + (1.f - decay) * bf2f(p[i]);
+    ema[i] = decay * ema[i] + omd * bf2f(p[i]);
 }
 }  // namespace
 
 void ema_update(torch::Tensor ema, torch::Tensor p, double decay) {
   TORCH_CHECK(ema.is_cuda() && ema.scalar_type() == torch::kFloat);
+  // both kernels index ema and p 0..ema.numel() as dense arrays
+  TORCH_CHECK(p.is_cuda() && p.get_device() == ema.get_device(),
+              "ema_update: p must be on ema's device");
+  TORCH_CHECK(p.scalar_type() == torch::kFloat ||
+              p.scalar_type() == torch::kBFloat16,
+              "ema_update: p must be fp32 or bf16");
+  TORCH_CHECK(p.numel() == ema.numel(), "ema_update: p has ", p.numel(),
+              " elements, ema has ", ema.numel());
+  TORCH_CHECK(ema.is_contiguous() && p.is_contiguous(),
+              "ema_update: ema and p must be contiguous");
   long n = ema.numel();
+  // 1 - decay in double, rounded once: 1.f - 0.9999f is 1.7e-4 off, and an
+  // EMA with weights that do not add up to 1 settles that far from p
+  const float omd = (float)(1.0 - decay);
   auto stream = at::cuda::getCurrentHIPStream();
   // vector path needs 16B-aligned ema and 16B/8B-aligned p: EMA views are
   // narrow() slices at arbitrary element offsets
@@ -321,29 +480,41 @@ void ema_update(torch::Tensor ema, torch::Tensor p, double decay) {
     hipLaunchKernelGGL(ema_bf16_kernel, dim3(ew_grid(n, 4)), dim3(BLOCK), 0,
                        stream, ema.data_ptr<float>(),
                        (const unsigned short*)p.data_ptr(), n, (float)decay,
-                       vec4);
+                       omd, vec4);
   } else {
     hipLaunchKernelGGL(ema_kernel, dim3(ew_grid(n, 4)), dim3(BLOCK), 0,
                        stream, ema.data_ptr<float>(), p.data_ptr<float>(), n,
-                       (float)decay, vec4);
+                       (float)decay, omd, vec4);
   }
   HIP_CHECK_LAST();
 }
 
 torch::Tensor l2norm_sq(torch::Tensor x) {
   TORCH_CHECK(x.is_cuda() && x.is_contiguous());
-  auto out = torch::zeros({}, x.options().dtype(torch::kFloat));
+  auto out = torch::empty({}, x.options().dtype(torch::kFloat));
   long n = x.numel();
+  const int grid = ew_grid(n);
+  // a single block's partial IS the result; otherwise a second one-block
+  // kernel adds the partials in index order
+  auto partial = grid == 1 ? out
+      : torch::empty({grid}, x.options().dtype(torch::kFloat));
   auto stream = at::cuda::getCurrentHIPStream();
   if (x.scalar_type() == torch::kBFloat16) {
-    hipLaunchKernelGGL(l2norm_kernel<bf16_t>, dim3(ew_grid(n)), dim3(BLOCK), 0,
+    hipLaunchKernelGGL(l2norm_kernel<bf16_t>, dim3(grid), dim3(BLOCK), 0,
                        stream, (const bf16_t*)x.data_ptr(),
-                       out.data_ptr<float>(), n);
+                       partial.data_ptr<float>(), n);
   } else {
-    hipLaunchKernelGGL(l2norm_kernel<float>, dim3(ew_grid(n)), dim3(BLOCK), 0,
-                       stream, x.data_ptr<float>(), out.data_ptr<float>(), n);
+    hipLaunchKernelGGL(l2norm_kernel<float>, dim3(grid), dim3(BLOCK), 0,
+                       stream, x.data_ptr<float>(), partial.data_ptr<float>(),
+                       n);
   }
   HIP_CHECK_LAST();
+  if (grid > 1) {
+    hipLaunchKernelGGL(l2norm_final_kernel, dim3(1), dim3(BLOCK), 0, stream,
+                       (const float*)partial.data_ptr<float>(),
+                       out.data_ptr<float>(), grid);
+    HIP_CHECK_LAST();
+  }
   return out;
 }
 
@@ -381,11 +552,13 @@ __global__ void multi_adamw_kernel(const int* __restrict__ cpid,
                                    int nchunks,
                                    float* __restrict__ m,
                                    float* __restrict__ v,
-                                   float lr, float beta1, float beta2,
-                                   float eps, float wd, float bc1, float bc2,
+                                   float beta1, float beta2, float eps,
+                                   AdamCoef ch,
+                                   const float* __restrict__ cdev,
                                    int param_bf16, int grad_bf16) {
   const int c = blockIdx.x;
   if (c >= nchunks) return;
+  const AdamCoef cf = adam_coef_load(ch, cdev);
   const int pid = cpid[c];
   const long off = coff[c];
   const long n = numels[pid];
@@ -427,14 +600,8 @@ __global__ void multi_adamw_kernel(const int* __restrict__ cpid,
       unsigned short* pbs = (unsigned short*)&pb;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        float pp_ = pi[j] * (1.f - lr * wd);
-        float mm_ = mi[j] * beta1 + gi[j] * (1.f - beta1);
-        float vv_ = vi[j] * beta2 + gi[j] * gi[j] * (1.f - beta2);
-        mi[j] = mm_;
-        vi[j] = vv_;
-        pp_ = pp_ - lr / bc1 * mm_ / (sqrtf(vv_ / bc2) + eps);
-        pi[j] = pp_;
-        pbs[j] = f2bf(pp_);
+        adam_elem(pi[j], mi[j], vi[j], gi[j], beta1, beta2, eps, cf);
+        pbs[j] = f2bf(pi[j]);
       }
       *(float4*)(m + k) = m4;
       *(float4*)(v + k) = v4;
@@ -448,12 +615,10 @@ __global__ void multi_adamw_kernel(const int* __restrict__ cpid,
       else if (grad_bf16) gi = bf2f(((const unsigned short*)gp)[i]);
       else gi = ((const float*)gp)[i];
       const long k = mvbase + i;
-      float pi = master[i] * (1.f - lr * wd);
-      float mi = m[k] * beta1 + gi * (1.f - beta1);
-      float vi = v[k] * beta2 + gi * gi * (1.f - beta2);
+      float pi = master[i], mi = m[k], vi = v[k];
+      adam_elem(pi, mi, vi, gi, beta1, beta2, eps, cf);
       m[k] = mi;
       v[k] = vi;
-      pi = pi - lr / bc1 * mi / (sqrtf(vi / bc2) + eps);
       master[i] = pi;
       if (param_bf16) ((unsigned short*)pp)[i] = f2bf(pi);
     }
@@ -465,17 +630,39 @@ __global__ void multi_adamw_kernel(const int* __restrict__ cpid,
     else if (grad_bf16) gi = bf2f(((const unsigned short*)gp)[i]);
     else gi = ((const float*)gp)[i];
     const long k = mvbase + i;
-    float pi = master[i] * (1.f - lr * wd);
-    float mi = m[k] * beta1 + gi * (1.f - beta1);
-    float vi = v[k] * beta2 + gi * gi * (1.f - beta2);
+    float pi = master[i], mi = m[k], vi = v[k];
+    adam_elem(pi, mi, vi, gi, beta1, beta2, eps, cf);
     m[k] = mi;
     v[k] = vi;
-    pi = pi - lr / bc1 * mi / (sqrtf(vi / bc2) + eps);
     master[i] = pi;
     if (param_bf16) ((unsigned short*)pp)[i] = f2bf(pi);
   }
 }
 
+}  // namespace
+
+namespace {
+void launch_multi_adamw(const torch::Tensor& cpid, const torch::Tensor& coff,
+                        const torch::Tensor& pptrs, const torch::Tensor& gptrs,
+                        const torch::Tensor& mptrs, const torch::Tensor& moffs,
+                        const torch::Tensor& numels, const torch::Tensor& m,
+                        const torch::Tensor& v, double beta1, double beta2,
+                        double eps, AdamCoef ch, const float* cdev,
+                        bool param_bf16, bool grad_bf16) {
+  TORCH_CHECK(m.is_cuda() && m.scalar_type() == torch::kFloat);
+  int nchunks = cpid.numel();
+  auto stream = at::cuda::getCurrentHIPStream();
+  hipLaunchKernelGGL(multi_adamw_kernel, dim3(nchunks), dim3(BLOCK), 0,
+                     stream, cpid.data_ptr<int>(), coff.data_ptr<long>(),
+                     pptrs.data_ptr<long>(), gptrs.data_ptr<long>(),
+                     mptrs.data_ptr<long>(), moffs.data_ptr<long>(),
+                     numels.data_ptr<long>(),
+                     nchunks, m.data_ptr<float>(),
+                     v.data_ptr<float>(), (float)beta1, (float)beta2,
+                     (float)eps, ch, cdev,
+                     param_bf16 ? 1 : 0, grad_bf16 ? 1 : 0);
+  HIP_CHECK_LAST();
+}
 }  // namespace
 
 void multi_adamw_step(torch::Tensor cpid, torch::Tensor coff,
@@ -486,19 +673,23 @@ void multi_adamw_step(torch::Tensor cpid, torch::Tensor coff,
                       long step, double lr, double beta1, double beta2,
                       double eps, double wd, bool param_bf16,
                       bool grad_bf16) {
-  TORCH_CHECK(m.is_cuda() && m.scalar_type() == torch::kFloat);
-  int nchunks = cpid.numel();
-  float bc1 = 1.f - powf((float)beta1, (float)step);
-  float bc2 = 1.f - powf((float)beta2, (float)step);
-  auto stream = at::cuda::getCurrentHIPStream();
-  hipLaunchKernelGGL(multi_adamw_kernel, dim3(nchunks), dim3(BLOCK), 0,
-                     stream, cpid.data_ptr<int>(), coff.data_ptr<long>(),
-                     pptrs.data_ptr<long>(), gptrs.data_ptr<long>(),
-                     mptrs.data_ptr<long>(), moffs.data_ptr<long>(),
-                     numels.data_ptr<long>(),
-                     nchunks, m.data_ptr<float>(),
-                     v.data_ptr<float>(), (float)lr, (float)beta1,
-                     (float)beta2, (float)eps, (float)wd, bc1, bc2,
-                     param_bf16 ? 1 : 0, grad_bf16 ? 1 : 0);
-  HIP_CHECK_LAST();
+  launch_multi_adamw(cpid, coff, pptrs, gptrs, mptrs, moffs, numels, m, v,
+                     beta1, beta2, eps,
+                     adam_coef_host(step, lr, beta1, beta2, wd), nullptr,
+                     param_bf16, grad_bf16);
+}
+
+// The capturable form: coefficients of this group from device memory
+// (written by adamw_prelude on the same stream).
+void multi_adamw_step_dev(torch::Tensor cpid, torch::Tensor coff,
+                          torch::Tensor pptrs, torch::Tensor gptrs,
+                          torch::Tensor mptrs, torch::Tensor moffs,
+                          torch::Tensor numels,
+                          torch::Tensor m, torch::Tensor v,
+                          torch::Tensor coef, double beta1, double beta2,
+                          double eps, bool param_bf16, bool grad_bf16) {
+  check_adam_coef(coef, m);
+  launch_multi_adamw(cpid, coff, pptrs, gptrs, mptrs, moffs, numels, m, v,
+                     beta1, beta2, eps, AdamCoef{}, coef.data_ptr<float>(),
+                     param_bf16, grad_bf16);
 }

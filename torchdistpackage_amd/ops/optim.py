@@ -11,6 +11,11 @@ fp32 flats (master weights, exp_avg, exp_avg_sq, grad buffer), so a step is
 
 instead of ~6 kernels x #params.  Profiling of the v0 per-param variant showed
 ~1900 cast + ~1700 copy kernels per 4 steps dominating step time.
+
+Known difference from stock torch: the optimizer keeps ONE global step count,
+where torch.optim.AdamW counts per parameter.  A parameter whose grad first
+appears at a late step (it was None until then) is therefore bias-corrected
+with the global count, not with 1 as in torch: its first updates are smaller.
 """
 
 from __future__ import annotations
@@ -84,6 +89,25 @@ class _FlatGroup:
 
 
 class FusedAdamW(torch.optim.Optimizer):
+    """AdamW over flat per-group state, one HIP kernel pass per flat.
+
+    hipGraph capture.  With params on a GPU the step count and every
+    group's ``lr`` (and ``weight_decay``) live in device memory.  Each
+    ``step()`` launches a one-block prelude kernel that advances the device
+    count and writes the group's fp32 coefficients ``1-beta1``, ``1-beta2``,
+    ``1-beta2^t``, ``lr/(1-beta1^t)`` and ``1-lr*wd`` (each formed in double,
+    rounded once) for the update kernels to read.  The prelude is part of
+    ``step()``, so a captured ``step()`` (``utils_graph.GraphedStep``) counts
+    and bias-corrects correctly on every replay.
+
+    ``group["lr"]`` / ``group["weight_decay"]`` are uploaded by an eager
+    ``step()`` whenever they changed.  A captured ``step()`` records no such
+    write (it would put the capture-time value back on every replay), so
+    between replays call :meth:`sync_lr` after changing them.  ``betas`` and
+    ``eps`` are kernel immediates: a captured graph keeps the values it was
+    captured with, and changing them needs a new capture.
+    """
+
     # Bf16ZeroOptimizer may attach a ``_tdpa_grad_override`` tensor to a
     # param instead of materializing a cast-copy into .grad: the
     # multi-tensor kernel reads grads by raw pointer with a dtype flag, so
@@ -97,7 +121,8 @@ class FusedAdamW(torch.optim.Optimizer):
                         weight_decay=weight_decay)
         super().__init__(params, defaults)
         self._flats: List[_FlatGroup] = []
-        self._step = 0
+        self._step_host = 0      # the count while no flat is on a GPU
+        self._dev = None         # device of the GPU flats, if any
         self._built = False
 
     def _build(self):
@@ -112,7 +137,51 @@ class FusedAdamW(torch.optim.Optimizer):
             for p in ps:
                 by_dtype.setdefault(p.dtype, []).append(p)
             group["_flats"] = [_FlatGroup(v) for v in by_dtype.values()]
+        devs = {fg.exp_avg.device for g in self.param_groups
+                for fg in g["_flats"] if fg.exp_avg.device.type == "cuda"}
+        if devs:
+            assert len(devs) == 1, f"params on several GPUs: {devs}"
+            self._dev = devs.pop()
+            G = len(self.param_groups)
+            self._step_dev = torch.full((1,), self._step_host,
+                                        dtype=torch.int64, device=self._dev)
+            self._hyp = torch.zeros(G, 4, dtype=torch.float64,
+                                    device=self._dev)
+            self._coef = torch.zeros(G, 5, dtype=torch.float32,
+                                     device=self._dev)
+            self._hyp_host = None
         self._built = True
+
+    @property
+    def _step(self) -> int:
+        """Steps taken so far (reads the device counter: a sync)."""
+        if self._dev is not None:
+            return int(self._step_dev.item())
+        return self._step_host
+
+    def _set_step(self, step: int):
+        if self._dev is not None:
+            self._step_dev.fill_(int(step))
+        else:
+            self._step_host = int(step)
+
+    def _host_hyp(self):
+        return [[float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]),
+                 float(g["weight_decay"])] for g in self.param_groups]
+
+    @torch.no_grad()
+    def sync_lr(self):
+        """Upload every group's ``lr`` and ``weight_decay`` to the device.
+        Eager steps do this themselves; call it between replays of a
+        captured ``step()`` after changing ``group["lr"]``.  Not to be
+        called while capturing."""
+        if not self._built:
+            self._build()
+        if self._dev is None:
+            return
+        host = self._host_hyp()
+        self._hyp.copy_(torch.tensor(host, dtype=torch.float64))
+        self._hyp_host = host
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -122,53 +191,96 @@ class FusedAdamW(torch.optim.Optimizer):
                 loss = closure()
         if not self._built:
             self._build()
-        self._step += 1
-        for group in self.param_groups:
+        if self._dev is not None:
+            from . import ext
+            if self._host_hyp() != self._hyp_host:
+                if torch.cuda.is_current_stream_capturing():
+                    raise RuntimeError(
+                        "FusedAdamW: lr/betas/weight_decay changed since "
+                        "the last eager step; call sync_lr() before "
+                        "capturing step()")
+                self.sync_lr()
+            ext("fused_adamw").adamw_prelude(self._step_dev, self._hyp,
+                                             self._coef)
+        else:
+            self._step_host += 1
+        for gi, group in enumerate(self.param_groups):
             for fg in group.get("_flats", []):
-                self._step_flat(group, fg)
+                self._step_flat(group, fg, gi)
         return loss
 
     @torch.no_grad()
-    def _step_flat(self, group, fg: _FlatGroup):
-        lr = group["lr"]
+    def _step_flat(self, group, fg: _FlatGroup, gi: int):
         beta1, beta2 = group["betas"]
-        def _grad(p):
-            ov = getattr(p, "_tdpa_grad_override", None)
-            return ov if ov is not None else p.grad
+        grads = []
+        for p in fg.params:
+            g = getattr(p, "_tdpa_grad_override", None)
+            grads.append(g if g is not None else p.grad)
+        on_gpu = fg.exp_avg.device.type == "cuda"
 
         if fg.mt_ready:
             from . import ext
-            key = tuple(_grad(p).data_ptr() if _grad(p) is not None else 0
-                        for p in fg.params)
+            # the kernel reads each grad by raw pointer as p.numel() dense
+            # elements of ONE dtype per flat
+            grad_dtype = None
+            for p, g in zip(fg.params, grads):
+                if g is None:
+                    continue
+                if g.numel() != p.numel() or not g.is_contiguous():
+                    raise ValueError(
+                        f"FusedAdamW: grad of shape {tuple(g.shape)}, "
+                        f"strides {g.stride()} for a param of shape "
+                        f"{tuple(p.shape)}: need a contiguous grad of "
+                        f"{p.numel()} elements")
+                if g.device != p.device:
+                    raise ValueError(f"FusedAdamW: grad on {g.device}, "
+                                     f"param on {p.device}")
+                if grad_dtype is None:
+                    grad_dtype = g.dtype
+                    if grad_dtype not in (torch.bfloat16, torch.float32):
+                        raise TypeError("FusedAdamW: grads must be bf16 or "
+                                        f"fp32, got {grad_dtype}")
+                elif g.dtype != grad_dtype:
+                    raise TypeError(
+                        f"FusedAdamW: grads of {grad_dtype} and {g.dtype} "
+                        f"in one {fg.uniform_dtype} flat; the kernel reads "
+                        "one grad dtype per flat")
+            key = tuple(g.data_ptr() if g is not None else 0 for g in grads)
             if getattr(fg, "_gptr_key", None) != key:
                 fg._gptr_key = key
                 fg._gptr_dev = torch.tensor(
                     list(key), dtype=torch.int64).to(fg.exp_avg.device)
             gptrs = fg._gptr_dev
-            grad_dtype = next((_grad(p).dtype for p in fg.params
-                               if _grad(p) is not None), fg.uniform_dtype)
-            ext("multi_adamw").multi_adamw_step(
+            if grad_dtype is None:
+                grad_dtype = fg.uniform_dtype
+            ext("multi_adamw").multi_adamw_step_dev(
                 fg.cpid, fg.coff, fg.pptrs, gptrs, fg.mptrs, fg.moffs,
-                fg.numels, fg.exp_avg, fg.exp_avg_sq, self._step, lr,
-                beta1, beta2, group["eps"], group["weight_decay"],
+                fg.numels, fg.exp_avg, fg.exp_avg_sq, self._coef[gi],
+                beta1, beta2, group["eps"],
                 fg.uniform_dtype == torch.bfloat16,
                 grad_dtype == torch.bfloat16)
         else:
-            grads = [_grad(p).to(p.dtype) if _grad(p) is not None
-                     else torch.zeros_like(p) for p in fg.params]
-            torch._foreach_copy_(fg.grad_views, grads)
+            g32 = [g.to(p.dtype) if g is not None
+                   else torch.zeros_like(p) for p, g in zip(fg.params, grads)]
+            torch._foreach_copy_(fg.grad_views, g32)
             # grad-None params must be SKIPPED (stock torch semantics): save
             # their flat segments and restore after the whole-flat update
             saves = []
             for i, p in enumerate(fg.params):
-                if _grad(p) is None:
+                if grads[i] is None:
                     o, n = fg.offs[i], p.numel()
                     saves.append((o, n, fg.master[o:o + n].clone(),
                                   fg.exp_avg[o:o + n].clone(),
                                   fg.exp_avg_sq[o:o + n].clone()))
-            fused_adamw_(fg.master, fg.grad32, fg.exp_avg, fg.exp_avg_sq,
-                         self._step, lr, beta1, beta2, group["eps"],
-                         group["weight_decay"])
+            if on_gpu:
+                from . import ext
+                ext("fused_adamw").adamw_step_dev(
+                    fg.master, fg.grad32, fg.exp_avg, fg.exp_avg_sq,
+                    self._coef[gi], beta1, beta2, group["eps"])
+            else:
+                fused_adamw_(fg.master, fg.grad32, fg.exp_avg,
+                             fg.exp_avg_sq, self._step, group["lr"], beta1,
+                             beta2, group["eps"], group["weight_decay"])
             for o, n, ms, es, vs in saves:
                 fg.master[o:o + n].copy_(ms)
                 fg.exp_avg[o:o + n].copy_(es)
@@ -199,7 +311,7 @@ class FusedAdamW(torch.optim.Optimizer):
     def load_state_dict(self, sd):
         if not self._built:
             self._build()
-        self._step = sd["step"]
+        self._set_step(sd["step"])
         for g, gsds in zip(self.param_groups, sd["groups"]):
             for fg, fsd in zip(g.get("_flats", []), gsds):
                 if fg.master is not None and fsd["master"] is not None:
