@@ -1,6 +1,7 @@
 """Input families, fp64 references and the error yardstick shared by
 tests/test_ops_numerics.py (CPU paths) and tests/test_ops_numerics_gpu.py
-(HIP kernels).
+(HIP kernels), the optimizer numerics files, and, from "Matmul family" on,
+tests/test_matmul_numerics.py and tests/test_matmul_numerics_gpu.py.
 
 Every generator is seeded and returns CPU tensors ALREADY ROUNDED to the
 dtype under test, so the fp64 reference is computed from exactly the values
@@ -605,3 +606,463 @@ def ema_err(got, ema, p, decay):
 # + 6 + 4 (wave, block) + 8 (per-thread partials) + 6 + 4 = 31 <= 64.
 
 FLOOR_L2NORM = 64 * 2.0 ** -24
+
+
+# ===========================================================================
+# Matmul family: GEMM / GEMV / decode attention / RoPE
+# (tests/test_matmul_numerics.py on the CPU, tests/test_matmul_numerics_gpu.py
+# on the HIP kernels; docs/design/kernels.md "Matmul-family numerics")
+# ===========================================================================
+
+# ------------------------------------------------------ exact-integer family
+#
+# Operands are integers in [-4, 4] stored in bf16 and K <= 16384, so every
+# product (<= 16) and every partial sum (<= 16 * 16384 = 2**18, plus a bias
+# of at most 4) is an integer below 2**24: fp32 accumulation is exact in ANY
+# order.  The only rounding is the final fp32 -> bf16, so the result must
+# equal the fp64 product rounded once, bit for bit.
+
+EXACT_MAX_K = 16384
+
+
+def int_mat(tag, shape, lo=-4, hi=4):
+    """Integers in [lo, hi] as bf16."""
+    g = _gen("int", tag, shape, lo, hi)
+    return torch.randint(lo, hi + 1, shape, generator=g).to(torch.bfloat16)
+
+
+def exact_mm_ref(A, B, bias=None):
+    """(A (M,K) @ B (N,K)^T [+ bias]) in fp64, rounded once to bf16."""
+    assert A.shape[1] == B.shape[1] <= EXACT_MAX_K
+    r = A.double().cpu() @ B.double().cpu().t()
+    if bias is not None:
+        r = r + bias.double().cpu()
+    return r.to(torch.bfloat16)
+
+
+def check_equal(got, ref, what):
+    """Bit equality of two tensors without NaN; reports the first
+    mismatching index."""
+    got, ref = got.detach().cpu(), ref.detach().cpu()
+    assert got.shape == ref.shape, \
+        f"{what}: shape {tuple(got.shape)} vs {tuple(ref.shape)}"
+    assert got.dtype == ref.dtype, f"{what}: dtype {got.dtype} vs {ref.dtype}"
+    if torch.equal(got, ref):
+        return
+    bad = (got != ref) | torch.isnan(got)
+    idx = tuple(bad.nonzero()[0].tolist())
+    raise AssertionError(
+        f"{what}: {int(bad.sum())} of {bad.numel()} elements differ, first "
+        f"at {idx}: got {got[idx].item()!r}, want {ref[idx].item()!r}")
+
+
+def gemm_operands(kind, A, B):
+    """The two tensors a GEMM binding of ``kind`` takes for the logical
+    product A (M,K) @ B (N,K)^T:
+      fprop  x (M,K),  w (N,K)
+      dgrad  dy (M,K), w (K,N)
+      wgrad  dy (K,M), x (K,N)"""
+    if kind == "fprop":
+        return A, B
+    if kind == "dgrad":
+        return A, B.t().contiguous()
+    assert kind == "wgrad"
+    return A.t().contiguous(), B.t().contiguous()
+
+
+# (tiles_m, tiles_n) -> what the 256x256 kernel does with the grid.  nwg is
+# tiles_m * tiles_n (* splitk); xcd_remap branches on nwg % 8.
+GEMM_GRIDS_FPROP = [(1, 1), (2, 1), (3, 1), (4, 1), (1, 3), (3, 3), (4, 2)]
+GEMM_GRIDS_DGRAD = [(1, 1), (3, 1), (2, 3)]
+GEMM_GRIDS_WGRAD = [(1, 1), (3, 2), (4, 1)]
+# nslot = K / 32 = 1..9: 1-3 a ring that never fills, 4-6 an empty main loop,
+# 7-9 the first main-loop group (ns_main = (nslot - 3) & ~3 = 4)
+GEMM_KS = [32, 64, 96, 128, 160, 224, 256, 288]
+
+
+def gemm_grid_id(tm, tn, splitk=1):
+    gsup = 4 if tm % 4 == 0 else (2 if tm % 2 == 0 else 1)
+    return f"grid{tm}x{tn}-gsup{gsup}-nwgmod8_{(tm * tn * splitk) % 8}"
+
+
+def gemm_k_id(K):
+    ns = K // 32
+    how = "ring_never_fills" if ns <= 3 else \
+        ("empty_main_loop" if ns <= 6 else "first_main_group")
+    return f"K{K}-nslot{ns}-{how}"
+
+
+# gemv: (M, N, K).  MT arms 1, 2, 4 (M=3 padded), 8 (M=5 padded), 16 (M=9
+# padded), 32 (M=17 padded).  The x tile is KT = 2048 for MT <= 16 and 1024
+# for MT = 32, so 2048 / 2056 / 4104 (resp. 1024 / 1032) sit on and just past
+# a tile edge; K = 8 and 16 leave most of the wave idle.  Odd N ends on the
+# ``two == false`` wave, N = 1 is that wave alone, N = 1000 is many blocks.
+GEMV_SHAPES = [
+    (1, 1, 8), (1, 7, 2048), (1, 1000, 2056),
+    (2, 9, 16), (2, 8, 2048), (2, 7, 4104),
+    (3, 1, 2056), (3, 9, 2048), (4, 1000, 4104), (4, 2, 1024),
+    (5, 7, 2048), (8, 9, 2056), (8, 1, 8), (8, 1000, 1032),
+    (9, 7, 2056), (9, 8, 2048), (16, 9, 4104), (16, 1, 16),
+    (17, 9, 1024), (17, 7, 1032), (32, 9, 1032), (32, 1, 1024),
+    (32, 1000, 2056), (32, 2, 8),
+]
+
+
+def gemv_id(shape):
+    M, N, K = shape
+    mt = next(t for t in (1, 2, 4, 8, 16, 32) if M <= t)
+    return f"M{M}-MT{mt}-N{N}{'-odd' if N % 2 else ''}-K{K}"
+
+
+def selection_matrix(tag, M, K):
+    """(A, idx): A (M, K) is 0/1 with A[i, idx[i]] = 1, idx a random map of
+    the M rows onto distinct columns when M <= K (a row-permuted selection)."""
+    g = _gen("sel", tag, M, K)
+    idx = torch.randperm(K, generator=g)[:M] if M <= K else \
+        torch.randint(0, K, (M,), generator=g)
+    A = torch.zeros(M, K, dtype=torch.bfloat16)
+    A[torch.arange(M), idx] = 1.0
+    return A, idx
+
+
+# --------------------------------------------------------- precision family
+#
+# Per-element error, so that an element that is small by cancellation is
+# judged against the size of the terms that cancel in it:
+#   e(t) = max_ij |t - ref|_ij / (2**-9 |ref|_ij + 2**-24 (|A| @ |B|^T)_ij)
+# and e(kernel) <= max(2.5 * e(library), 1.0).  A correctly rounded bf16
+# result has |t - ref| <= 2**-8 |ref| (8 significand bits), i.e. e <= 2, and
+# the library measures 1.9-2.0 on every family, so 2.5 * e(library) is the
+# active term and the floor of 1.0 never widens the bound.
+
+MM_FAMILIES = ["randn", "shift", "cancel", "wide"]
+FLOOR_MM = 1.0
+
+
+def mm_input(family, M, N, K):
+    """bf16 A (M,K), B (N,K)."""
+    g = _gen("mm", family, M, N, K)
+    A, B = _randn((M, K), g), _randn((N, K), g)
+    if family == "randn":
+        pass
+    elif family == "shift":       # mean 8: sums are large, fp32 error shows
+        A, B = 8.0 + A, 8.0 + B
+    elif family == "cancel":      # columns in +- pairs: ref ~ 0, |A||B| large
+        A, B = A.to(torch.bfloat16).double(), B.to(torch.bfloat16).double()
+        A[:, 1::2] = -A[:, 0::2]
+        B[:, 1::2] = B[:, 0::2] + 2.0 ** -5 * _randn((N, K // 2), g)
+    elif family == "wide":        # per-row scales 2**-6 .. 2**6
+        sa = 2.0 ** torch.randint(-6, 7, (M, 1), generator=g).double()
+        sb = 2.0 ** torch.randint(-6, 7, (N, 1), generator=g).double()
+        A, B = A * sa, B * sb
+    else:
+        raise KeyError(family)
+    return A.to(torch.bfloat16), B.to(torch.bfloat16)
+
+
+def mm_ref_mag(A, B, bias=None):
+    """fp64 (A @ B^T [+ bias], |A| @ |B|^T [+ |bias|])."""
+    A64, B64 = A.double().cpu(), B.double().cpu()
+    ref = A64 @ B64.t()
+    mag = A64.abs() @ B64.abs().t()
+    if bias is not None:
+        ref = ref + bias.double().cpu()
+        mag = mag + bias.double().cpu().abs()
+    return ref, mag
+
+
+def mm_err(t, ref, mag):
+    t = t.detach().double().cpu()
+    assert t.shape == ref.shape
+    assert torch.isfinite(t).all(), "result is not finite"
+    return ((t - ref).abs() / (2.0 ** -9 * ref.abs() + 2.0 ** -24 * mag)) \
+        .max().item()
+
+
+def mm_check(got, lib, ref, mag, what):
+    """Assert e(got) <= max(2.5 * e(lib), 1.0).  Returns (e_got, e_lib)."""
+    e_got, e_lib = mm_err(got, ref, mag), mm_err(lib, ref, mag)
+    bound = max(MARGIN * e_lib, FLOOR_MM)
+    print(f"NUMERICS {what}: e_got={e_got:.3e} e_lib={e_lib:.3e} "
+          f"bound={bound:.3e}")
+    assert e_got <= bound, \
+        f"{what}: e(got)={e_got:.3e} > max({MARGIN}*e(lib)={e_lib:.3e}, " \
+        f"floor={FLOOR_MM})"
+    return e_got, e_lib
+
+
+# --------------------------------------------------- decode-attention needles
+#
+# q rows are +-1 Walsh patterns; the needle key of a row is 4 * its pattern,
+# every other key is +-0.25 at random, v lies in [1, 2) and is distinct per
+# key.  With scale 1/sqrt(D) the needle scores 4*sqrt(D) (32 at D = 64) and
+# any other key at most sqrt(D)/4 in magnitude (2), the needle of another row
+# exactly 0 (Walsh rows are orthogonal): a lead of >= 30 nats, > 43 bits.
+# Over <= 4160 keys everything else weighs < 4160 * 2**-43 < 2**-30 of the
+# result, far below half a bf16 ulp (2**-9), and v, being a bf16 number, sits
+# at the centre of its rounding interval: the output row must be the needle's
+# v row bit for bit.
+
+NEEDLE_SMAX = [1, 40, 72, 200, 256]
+# (Hq, Hkv, Sq): M = (Hq / Hkv) * Sq = 1, 2, 4, 6 (padded MT 8), 8, 16
+NEEDLE_HEADS = [(2, 2, 1), (2, 2, 2), (8, 2, 1), (6, 2, 2), (8, 2, 2),
+                (8, 2, 4)]
+
+
+def _walsh(D):
+    H = torch.ones(1, 1, dtype=torch.float64)
+    while H.shape[0] < D:
+        H = torch.cat([torch.cat([H, H], 1), torch.cat([H, -H], 1)], 0)
+    assert H.shape[0] == D
+    return H
+
+
+def needle_probe_positions(L):
+    """Key positions probed in a cache of L visible keys: all of them up to
+    72, otherwise both sides of every 64-chunk edge, both ends, and a stride
+    of 7 in between."""
+    if L <= 72:
+        return list(range(L))
+    pos = set(range(0, L, 7)) | {0, 1, L - 2, L - 1}
+    for e in range(64, L + 1, 64):
+        pos |= {e - 2, e - 1, e, e + 1}
+    return sorted(p for p in pos if 0 <= p < L)
+
+
+def needle_input(tag, D, Hq, Hkv, Sq, Smax, pos0, needles):
+    """One needle per (batch row, kv head, pattern).
+
+    ``pos0``: list of B ints, row i of batch b sees keys [0, pos0[b] + i].
+    ``needles``: (B, P) int positions, distinct within a batch row; query row
+    m = g * Sq + i of a kv head carries pattern m % P and must return the v
+    row of key needles[b, m % P].
+
+    Returns (q, k_base, v_base, want): q (B, Hq, Sq, D) bf16; the caches are
+    ``k_base.narrow(2, 16, Smax)`` / ``v_base.narrow(2, 24, Smax)`` of
+    NaN-margined allocations, NaN from key pos0[b] + Sq on; want
+    (B, Hq, Sq, D) bf16."""
+    g = _gen("needle", tag, D, Hq, Hkv, Sq, Smax)
+    B = len(pos0)
+    G = Hq // Hkv
+    needles = torch.as_tensor(needles, dtype=torch.long).reshape(B, -1)
+    P = needles.shape[1]
+    W = _walsh(D)
+    nan = float("nan")
+    kb = torch.full((B, Hkv, Smax + 32, D), nan, dtype=torch.float64)
+    vb = torch.full((B, Hkv, Smax + 48, D), nan, dtype=torch.float64)
+    k, v = kb.narrow(2, 16, Smax), vb.narrow(2, 24, Smax)
+    j = torch.arange(Smax)
+    q = torch.empty(B, Hkv, G * Sq, D, dtype=torch.float64)
+    want = torch.empty(B, Hkv, G * Sq, D, dtype=torch.float64)
+    for b in range(B):
+        L = pos0[b] + Sq
+        assert 0 <= pos0[b] and L <= Smax
+        assert len(set(needles[b].tolist())) == P
+        kk = 0.25 * (torch.randint(0, 2, (Hkv, L, D), generator=g) * 2 - 1)
+        vv = 1.0 + torch.randint(0, 128, (Hkv, L, D), generator=g) / 128.0
+        vv[:, :, 0] = 1.0 + (j[:L] % 128) / 128.0          # distinct per key
+        vv[:, :, 1] = 1.0 + (j[:L] // 128) / 128.0
+        vv[:, :, 2] = 1.0 + torch.arange(Hkv)[:, None] / 128.0
+        for h in range(Hkv):
+            for p in range(P):
+                n = int(needles[b, p])
+                assert 0 <= n < L
+                kk[h, n] = 4.0 * W[1 + (h * 16 + p) % (D - 1)]
+            for m in range(G * Sq):
+                p = m % P
+                q[b, h, m] = W[1 + (h * 16 + p) % (D - 1)]
+                want[b, h, m] = vv[h, int(needles[b, p])]
+        k[b, :, :L] = kk
+        v[b, :, :L] = vv
+    bf = torch.bfloat16
+    return (q.reshape(B, Hq, Sq, D).to(bf), kb.to(bf), vb.to(bf),
+            want.reshape(B, Hq, Sq, D).to(bf))
+
+
+def needle_views(kb, vb, Smax):
+    kc, vc = kb.narrow(2, 16, Smax), vb.narrow(2, 24, Smax)
+    return kc, vc
+
+
+def needle_grid(Smax, Sq, M):
+    """(pos0 list, needles (B, P)) for two calls on one cache size:
+    'full'  every batch row has all Smax keys; row b's first needle sits on
+            probe position b (the others are spread behind it)
+    'ragged' batch row b is one probe length long and its first needle is its
+            LAST visible-to-all key."""
+    out = {}
+    vis = Smax - Sq + 1                 # keys every query row sees
+    P = min(M, vis)
+    step = vis // P
+    probes = needle_probe_positions(vis)
+    out["full"] = ([Smax - Sq] * len(probes),
+                   [[(b + p * step) % vis for p in range(P)] for b in probes])
+    pos0, needles = [], []
+    for n in probes:                    # n + 1 keys visible to every row
+        Pn = min(M, n + 1)
+        if Pn < P:
+            continue                    # one P per call
+        st = (n + 1) // P
+        pos0.append(n)
+        needles.append([(n - p * st) % (n + 1) for p in range(P)])
+    out["ragged"] = (pos0, needles)
+    return out
+
+
+def check_needles(got, want, what):
+    """Every output row must be its needle's v row, bit for bit."""
+    got, want = got.detach().cpu(), want.detach().cpu()
+    assert got.shape == want.shape and got.dtype == want.dtype
+    if torch.equal(got.contiguous(), want.contiguous()):
+        return
+    bad = ((got != want) | torch.isnan(got)).any(-1)
+    idx = tuple(bad.nonzero()[0].tolist())
+    raise AssertionError(
+        f"{what}: {int(bad.sum())} of {bad.numel()} rows are not their "
+        f"needle's v row, first (batch, head, row) = {idx}: got "
+        f"{got[idx][:4].tolist()}..., want {want[idx][:4].tolist()}...")
+
+
+def multi_needle_input(tag, D, Smax, positions, M=1):
+    """B = 1, Hkv = 1, Hq = M, Sq = 1: every q row is the same pattern and
+    the n = 2 or 4 keys at ``positions`` all carry 4 * pattern, so the output
+    must be the exact mean of their v rows.  Their bf16 mantissas are made
+    multiples of n, so the mean is a bf16 number.  Returns
+    (q, k_base, v_base, want)."""
+    n = len(positions)
+    assert n in (2, 4) and len(set(positions)) == n
+    q, kb, vb, _ = needle_input(tag, D, M, 1, 1, Smax, [Smax - 1],
+                                [[positions[0]]])
+    k, v = needle_views(kb, vb, Smax)
+    q[:] = q[0, 0]
+    step = 128.0 / n
+    for i, pos in enumerate(positions):
+        k[0, 0, pos] = k[0, 0, positions[0]]
+        row = (v[0, 0, pos].double() * step).floor() / step
+        row[3] = 1.0 + i * n / 128.0                     # distinct rows
+        v[0, 0, pos] = row.to(v.dtype)
+    mean = sum(v[0, 0, pos].double() for pos in positions) / n
+    want = mean.to(torch.bfloat16)
+    assert torch.equal(want.double(), mean)
+    return q, kb, vb, want.expand(1, M, 1, D)
+
+
+MULTI_NEEDLES = [      # (positions in a 256-key cache, what they pin)
+    ((3, 12), "two waves of one split"),
+    ((5, 37), "one lane group, two steps"),
+    ((63, 64), "last key of a chunk and first key of the next"),
+    ((63, 100), "two neighbouring splits"),
+    ((10, 250), "first and last split"),
+    ((3, 12, 20, 100), "three needles in one split, one in the next: "
+                       "the merge must weigh by l"),
+]
+
+
+def causal_needle_input(tag, D, G, Sq, Smax, pos0, istar):
+    """B = 1, Hkv = 1, Hq = G.  Group g's needle sits at key pos0 + istar[g]
+    (distinct per group), so rows i >= istar[g] of group g must return its v
+    row exactly and rows i < istar[g] do not see it.  Returns
+    (q, k_base, v_base, want, exact) with exact a (1, G, Sq) bool mask."""
+    assert len(istar) == G and len(set(istar)) == G and max(istar) < Sq
+    q, kb, vb, _ = needle_input(tag, D, G, 1, Sq, Smax, [pos0], [[0]])
+    k, v = needle_views(kb, vb, Smax)
+    W = _walsh(D)
+    k[0, 0, 0] = 0.25 * W[D - 1]          # undo needle_input's own needle
+    want = torch.zeros(1, G, Sq, D, dtype=torch.bfloat16)
+    exact = torch.zeros(1, G, Sq, dtype=torch.bool)
+    for g_ in range(G):
+        n = pos0 + istar[g_]
+        q[0, g_] = W[1 + g_]
+        k[0, 0, n] = 4.0 * W[1 + g_]
+        want[0, g_] = v[0, 0, n]
+        exact[0, g_, istar[g_]:] = True
+    return q, kb, vb, want, exact
+
+
+def decode_ref64(q, kc, vc, pos0, scale=None):
+    """fp64 decode attention on the CPU (NaN tails allowed).  (B,Hq,Sq,D)."""
+    B, Hq, Sq, D = q.shape
+    Hkv, Smax = kc.shape[1], kc.shape[2]
+    G = Hq // Hkv
+    scale = scale or 1.0 / math.sqrt(D)
+    out = torch.empty(B, Hkv, G * Sq, D, dtype=torch.float64)
+    q64 = q.double().cpu().reshape(B, Hkv, G * Sq, D)
+    for b in range(B):
+        L = pos0[b] + Sq
+        k = kc[b, :, :L].double().cpu()
+        v = vc[b, :, :L].double().cpu()
+        s = q64[b] @ k.transpose(-1, -2) * scale            # (Hkv, M, L)
+        row = torch.arange(G * Sq) % Sq
+        vis = torch.arange(L)[None, :] <= (pos0[b] + row[:, None])
+        s = s.masked_fill(~vis, float("-inf"))
+        out[b] = torch.softmax(s, -1) @ v
+    return out.reshape(B, Hq, Sq, D)
+
+
+# ---------------------------------------------------------------------- RoPE
+
+ROPE_DIMS = [16, 64, 80, 128]
+ROPE_FAMILIES = ["randn", "wide", "rotation"]
+
+
+def rope_tables(rows, D, base=10000.0):
+    """fp32 (rows, D/2) cos / sin with position- and d-dependent entries;
+    row 0 is cos = 1, sin = 0."""
+    inv = 1.0 / (base ** (torch.arange(0, D, 2, dtype=torch.float64) / D))
+    fr = torch.outer(torch.arange(rows, dtype=torch.float64), inv)
+    return fr.cos().float(), fr.sin().float()
+
+
+def rope_input(family, shape):
+    """bf16 x of ``shape`` (..., D) and a dy of the same shape."""
+    g = _gen("rope", family, shape)
+    D = shape[-1]
+    x = _randn(shape, g)
+    if family == "randn":
+        pass
+    elif family == "wide":
+        x = x * 2.0 ** torch.randint(-6, 7, shape[:-1] + (1,),
+                                     generator=g).double()
+    elif family == "rotation":    # every (x1, x2) pair is a unit vector
+        phi = x[..., :D // 2] * math.pi
+        x = torch.cat([phi.cos(), phi.sin()], -1)
+    else:
+        raise KeyError(family)
+    return x.to(torch.bfloat16), _randn(shape, g).to(torch.bfloat16)
+
+
+def rope_formula(x, cos, sin, pos0):
+    """Eager rotate-half over (..., S, D) in x's dtype with the table rows
+    cast to it.  Differentiable."""
+    S, hd = x.shape[-2], x.shape[-1]
+    c = cos[pos0:pos0 + S].to(device=x.device, dtype=x.dtype)
+    s = sin[pos0:pos0 + S].to(device=x.device, dtype=x.dtype)
+    x1, x2 = x[..., :hd // 2], x[..., hd // 2:]
+    return torch.cat([x1 * c - x2 * s, x2 * c + x1 * s], dim=-1)
+
+
+def rope_lib(x, cos, sin, pos0):
+    """The yardstick: rotate-half in fp32, rounded once to x's dtype."""
+    return rope_formula(x.float(), cos, sin, pos0).to(x.dtype)
+
+
+def rope_all_bf16(x, cos, sin, pos0):
+    """Tables and every product rounded to bf16 (the CPU fallback's formula
+    before it moved to fp32).  Kept as the teeth check."""
+    assert x.dtype == torch.bfloat16
+    return rope_formula(x, cos, sin, pos0)
+
+
+def rope_case(family, D, layout, B=2, H=3, S=5):
+    """(x, dy, cos, sin, view): ``view(x)`` is the (B, H, S, D) tensor the op
+    sees.  layout "contiguous", or "permuted": the Llama projection output
+    (S, B, H*D) read in place as (B, H, S, D).  Tables have S + 8 rows."""
+    cos, sin = rope_tables(S + 8, D)
+    if layout == "contiguous":
+        x, dy = rope_input(family, (B, H, S, D))
+        return x, dy, cos, sin, lambda t: t
+    assert layout == "permuted"
+    x, _ = rope_input(family, (S, B, H * D))
+    _, dy = rope_input(family, (B, H, S, D))
+    return x, dy, cos, sin, \
+        lambda t: t.view(S, B, H, D).permute(1, 2, 0, 3)

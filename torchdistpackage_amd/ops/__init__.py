@@ -719,6 +719,17 @@ def batched_bias_gelu(x, bias):
     return _BatchedBiasGeluFn.apply(x, bias)
 
 
+def _rope_rows(cos, sin, pos0, S):
+    """fp32 table rows [pos0, pos0+S) for the CPU path, range-checked like
+    the kernel binding."""
+    if cos.shape != sin.shape:
+        raise ValueError("rope: sin must have the shape of cos")
+    if pos0 < 0 or pos0 + S > cos.shape[0]:
+        raise ValueError(f"rope: pos0={pos0} with S={S} outside the cos/sin "
+                         f"table ({cos.shape[0]} rows)")
+    return cos[pos0:pos0 + S].float(), sin[pos0:pos0 + S].float()
+
+
 class _RopeFn(torch.autograd.Function):
     """Rotate-half RoPE over (B, H, S, D) with fp32 (S, D/2) tables."""
 
@@ -730,12 +741,13 @@ class _RopeFn(torch.autograd.Function):
             # strided input is read in place (head dim must be contiguous);
             # output is contiguous (B, H, S, D)
             return ext("rope").rope_apply(x, cos, sin, pos0, True)
+        # fp32 tables, fp32 products, one rounding: the kernel's arithmetic
+        c, s = _rope_rows(cos, sin, pos0, x.shape[-2])
         hd = x.shape[-1]
-        S = x.shape[-2]
-        c = cos[pos0:pos0 + S].to(x.dtype)
-        s = sin[pos0:pos0 + S].to(x.dtype)
-        x1, x2 = x[..., :hd // 2], x[..., hd // 2:]
-        return torch.cat([x1 * c - x2 * s, x2 * c + x1 * s], dim=-1)
+        xf = x.float()
+        x1, x2 = xf[..., :hd // 2], xf[..., hd // 2:]
+        return torch.cat([x1 * c - x2 * s, x2 * c + x1 * s],
+                         dim=-1).to(x.dtype)
 
     @staticmethod
     def backward(ctx, dy):
@@ -746,12 +758,12 @@ class _RopeFn(torch.autograd.Function):
             return (ext("rope").rope_apply(dy, cos, sin,
                                            ctx.pos0, False),
                     None, None, None)
+        c, s = _rope_rows(cos, sin, ctx.pos0, dy.shape[-2])
         hd = dy.shape[-1]
-        S = dy.shape[-2]
-        c = cos[ctx.pos0:ctx.pos0 + S].to(dy.dtype)
-        s = sin[ctx.pos0:ctx.pos0 + S].to(dy.dtype)
-        d1, d2 = dy[..., :hd // 2], dy[..., hd // 2:]
-        return (torch.cat([d1 * c + d2 * s, d2 * c - d1 * s], dim=-1),
+        df = dy.float()
+        d1, d2 = df[..., :hd // 2], df[..., hd // 2:]
+        return (torch.cat([d1 * c + d2 * s, d2 * c - d1 * s],
+                          dim=-1).to(dy.dtype),
                 None, None, None)
 
 
@@ -763,7 +775,9 @@ def rope_rotate_half(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
     ``pos0`` may be a 1-element long DEVICE tensor (inference only): the
     kernel reads the position at run time, which keeps the op
     hipGraph-capturable (inference/generate.py's graphed Llama decoder
-    advances the tensor in place between replays)."""
+    advances the tensor in place between replays).  A host position must
+    keep ``pos0 + S`` inside the tables (it raises otherwise); a device
+    position is clamped to ``[0, rows - S]`` by the kernel."""
     if torch.is_tensor(pos0):
         assert not torch.is_grad_enabled(), \
             "tensor pos0 is the no-grad decode path"

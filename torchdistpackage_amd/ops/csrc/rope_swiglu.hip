@@ -45,14 +45,21 @@ __global__ void rope_kernel(const unsigned short* __restrict__ x,
                             const float* __restrict__ cs,   // (S, D/2) cos
                             const float* __restrict__ sn,   // (S, D/2) sin
                             long rows, int S, int D, int pos0,
-                            long H, long xsb, long xsh, long xss,
+                            int pos_max, long H, long xsb, long xsh, long xss,
                             const long* __restrict__ pos0p) {
   const int half = D >> 1;
   const int chunks = half >> 3;                 // 8 elems per thread-chunk
   const long total = rows * chunks;
   // pos0p: optional DEVICE position (hipGraph-capturable decode — the
-  // graph replays with the position tensor advanced in place)
-  const int p0 = pos0p ? (int)*pos0p : pos0;
+  // graph replays with the position tensor advanced in place).  Nothing
+  // bounds that tensor on the host, so it is clamped to [0, pos_max]
+  // (pos_max = table rows - S) before any address is formed, as
+  // da_read_pos in decode_attn.hip does.
+  int p0 = pos0;
+  if (pos0p) {
+    const long p = *pos0p;
+    p0 = (int)(p < 0 ? 0 : (p > (long)pos_max ? (long)pos_max : p));
+  }
   for (long g = (long)blockIdx.x * blockDim.x + threadIdx.x; g < total;
        g += (long)gridDim.x * blockDim.x) {
     const long row = g / chunks;
@@ -192,20 +199,50 @@ void check_bf16(const torch::Tensor& t, const char* n) {
 
 }  // namespace
 
-// x (B, H, S, D) bf16 contiguous; cos/sin (>=S+pos0, D/2) fp32.
-torch::Tensor rope_apply(torch::Tensor x, torch::Tensor cs, torch::Tensor sn,
-                         long pos0, bool fwd) {
+// Everything both entry points check before a launch.  The kernel reads x
+// with 16-byte accesses at xbase + {0, D/2} (c and D/2 are multiples of 8
+// elements) and the tables with float4, so the x strides, the x base pointer
+// and the table base pointers must keep those aligned; the tables must live
+// where the kernel runs.
+static void rope_check(const torch::Tensor& x, const torch::Tensor& cs,
+                       const torch::Tensor& sn) {
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == torch::kBFloat16 &&
               x.dim() == 4 && x.stride(3) == 1,
               "rope: x must be 4-D bf16 CUDA with contiguous head dim");
+  TORCH_CHECK(cs.device() == x.device() && sn.device() == x.device(),
+              "rope: cos/sin tables must be on x's device");
   TORCH_CHECK(cs.scalar_type() == torch::kFloat &&
-              cs.is_contiguous() && sn.is_contiguous());
+              sn.scalar_type() == torch::kFloat && cs.dim() == 2 &&
+              cs.is_contiguous() && sn.is_contiguous(),
+              "rope: cos/sin must be contiguous 2-D fp32 tables");
+  TORCH_CHECK(sn.sizes() == cs.sizes(),
+              "rope: sin must have the shape of cos");
+  const long D = x.size(3);
+  TORCH_CHECK(D % 16 == 0 && cs.size(1) == D / 2,
+              "rope: head dim must be a multiple of 16 and the tables "
+              "(rows, D/2)");
+  // (the stride of a size-1 dim is never multiplied by a non-zero index)
+  auto stride_ok = [&](int d) {
+    return x.size(d) <= 1 || x.stride(d) % 8 == 0;
+  };
+  TORCH_CHECK(stride_ok(0) && stride_ok(1) && stride_ok(2) &&
+              reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0 &&
+              reinterpret_cast<uintptr_t>(cs.data_ptr()) % 16 == 0 &&
+              reinterpret_cast<uintptr_t>(sn.data_ptr()) % 16 == 0,
+              "rope: x strides must be multiples of 8 elements and the x, "
+              "cos and sin base pointers 16-byte aligned");
+}
+
+static torch::Tensor rope_launch(const torch::Tensor& x,
+                                 const torch::Tensor& cs,
+                                 const torch::Tensor& sn, long pos0,
+                                 const long* pos0p, bool fwd) {
   const int D = x.size(3), S = x.size(2);
-  TORCH_CHECK(D % 16 == 0 && cs.size(1) == D / 2);
   const long rows = (long)x.size(0) * x.size(1) * S;
   auto y = torch::empty({x.size(0), x.size(1), x.size(2), x.size(3)},
                         x.options());
   const long total = rows * (D / 16);
+  if (total == 0) return y;
   const long nb = (total + BLOCK - 1) / BLOCK;
   auto stream = at::cuda::getCurrentHIPStream();
   auto kern = fwd ? rope_kernel<true> : rope_kernel<false>;
@@ -214,41 +251,36 @@ torch::Tensor rope_apply(torch::Tensor x, torch::Tensor cs, torch::Tensor sn,
                      (const unsigned short*)x.data_ptr(),
                      (unsigned short*)y.data_ptr(), cs.data_ptr<float>(),
                      sn.data_ptr<float>(), rows, S, D, (int)pos0,
+                     (int)(cs.size(0) - S),
                      x.size(1), x.stride(0), x.stride(1), x.stride(2),
-                     (const long*)nullptr);
+                     pos0p);
   HIP_CHECK_LAST();
   return y;
+}
+
+// x (B, H, S, D) bf16, head dim contiguous; cos/sin (>=S+pos0, D/2) fp32.
+torch::Tensor rope_apply(torch::Tensor x, torch::Tensor cs, torch::Tensor sn,
+                         long pos0, bool fwd) {
+  rope_check(x, cs, sn);
+  TORCH_CHECK(pos0 >= 0 && pos0 + x.size(2) <= cs.size(0),
+              "rope: pos0=", pos0, " with S=", x.size(2),
+              " outside the cos/sin table (", cs.size(0), " rows)");
+  return rope_launch(x, cs, sn, pos0, nullptr, fwd);
 }
 
 torch::Tensor rope_apply_pos(torch::Tensor x, torch::Tensor cs,
                              torch::Tensor sn, torch::Tensor pos,
                              bool fwd) {
-  // device-position variant for hipGraph-captured decode
-  TORCH_CHECK(x.is_cuda() && x.scalar_type() == torch::kBFloat16 &&
-              x.dim() == 4 && x.stride(3) == 1,
-              "rope: x must be 4-D bf16 CUDA with contiguous head dim");
-  TORCH_CHECK(cs.scalar_type() == torch::kFloat &&
-              cs.is_contiguous() && sn.is_contiguous());
-  TORCH_CHECK(pos.is_cuda() && pos.scalar_type() == torch::kLong &&
-              pos.numel() == 1);
-  const int D = x.size(3), S = x.size(2);
-  TORCH_CHECK(D % 16 == 0 && cs.size(1) == D / 2);
-  const long rows = (long)x.size(0) * x.size(1) * S;
-  auto y = torch::empty({x.size(0), x.size(1), x.size(2), x.size(3)},
-                        x.options());
-  const long total = rows * (D / 16);
-  const long nb = (total + BLOCK - 1) / BLOCK;
-  auto stream = at::cuda::getCurrentHIPStream();
-  auto kern = fwd ? rope_kernel<true> : rope_kernel<false>;
-  hipLaunchKernelGGL(kern, dim3((unsigned)std::min(nb, (long)65535 * 8)),
-                     dim3(BLOCK), 0, stream,
-                     (const unsigned short*)x.data_ptr(),
-                     (unsigned short*)y.data_ptr(), cs.data_ptr<float>(),
-                     sn.data_ptr<float>(), rows, S, D, 0,
-                     x.size(1), x.stride(0), x.stride(1), x.stride(2),
-                     (const long*)pos.data_ptr());
-  HIP_CHECK_LAST();
-  return y;
+  // device-position variant for hipGraph-captured decode; the kernel clamps
+  // the position it reads to [0, rows - S]
+  rope_check(x, cs, sn);
+  TORCH_CHECK(pos.device() == x.device() &&
+              pos.scalar_type() == torch::kLong && pos.numel() == 1,
+              "rope: pos must be a 1-element int64 tensor on x's device");
+  TORCH_CHECK(x.size(2) <= cs.size(0),
+              "rope: S=", x.size(2), " exceeds the cos/sin table (",
+              cs.size(0), " rows)");
+  return rope_launch(x, cs, sn, 0, (const long*)pos.data_ptr(), fwd);
 }
 
 torch::Tensor swiglu_fwd(torch::Tensor a, torch::Tensor b) {
