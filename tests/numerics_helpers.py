@@ -1,7 +1,9 @@
 """Input families, fp64 references and the error yardstick shared by
 tests/test_ops_numerics.py (CPU paths) and tests/test_ops_numerics_gpu.py
 (HIP kernels), the optimizer numerics files, and, from "Matmul family" on,
-tests/test_matmul_numerics.py and tests/test_matmul_numerics_gpu.py.
+tests/test_matmul_numerics.py and tests/test_matmul_numerics_gpu.py, and, from
+"training attention: exact inputs" on, tests/test_attention_numerics.py and
+tests/test_attention_numerics_gpu.py.
 
 Every generator is seeded and returns CPU tensors ALREADY ROUNDED to the
 dtype under test, so the fp64 reference is computed from exactly the values
@@ -1066,3 +1068,517 @@ def rope_case(family, D, layout, B=2, H=3, S=5):
     _, dy = rope_input(family, (B, H, S, D))
     return x, dy, cos, sin, \
         lambda t: t.view(S, B, H, D).permute(1, 2, 0, 3)
+
+
+# ---------------------------------------- training attention: exact inputs
+#
+# The decode needle idea carried to the training kernels.  q rows are +-1
+# Walsh patterns, the target key of a row is 4 * its pattern, every other key
+# is +-0.25 at random, scale = 1/sqrt(D).  The target scores 4*sqrt(D), any
+# random key at most sqrt(D)/4 in magnitude and the target of another pattern
+# exactly 0, so the target leads by >= 4*sqrt(D) - sqrt(D)/4 nats (30 at
+# D = 64, e**-30 < 1e-13).  Then
+#   o    is the target's v row bit for bit (v is a bf16 number and everything
+#        else weighs < 2**-30 of it),
+#   dv   at a key is the sum of do over the rows that chose it.  do holds
+#        integers in [-4, 4] and the sum is kept exactly representable in
+#        bf16, so |dv - sum| <= 2**-24 (a sum that is exactly 0 still picks
+#        up e**-30-sized terms, hence not bit-equal),
+#   dS   at the target is P * (dP - delta) with dP = do . v_target and
+#        delta = do . o = do . v_target: both are sums of multiples of 2**-7
+#        below 2**11, exact in fp32 in any order, so dS is exactly 0 if the
+#        kernel takes dP and delta from the same row; elsewhere P <= e**-30.
+#        Hence |dq|, |dk| <= 2**-20 everywhere.
+# The tie input gives each pattern two keys 4*W[1+p] +- 2*W[D/2+p] that both
+# score exactly 4*sqrt(D): o must be (v_a + v_b) / 2 bit for bit (v on
+# multiples of 2**-6, so the mean is a bf16 number), which pins the
+# online-softmax rescale at equal maxima across two key tiles, and dq/dk are
+# O(1) and checked per element against fp64 (``check_train_case``).
+
+TRAIN_EDGE = 32              # targets sit on both sides of every multiple
+TRAIN_TIE_GAP = 65           # distance between the two keys of a tie pair
+BOUND_TRAIN_DV = 2.0 ** -24
+BOUND_TRAIN_ZERO = 2.0 ** -20
+
+
+def _train_candidates(S):
+    pos = {0, 1, S - 2, S - 1}
+    for e in range(TRAIN_EDGE, S, TRAIN_EDGE):
+        pos |= {e - 1, e}
+    return sorted(p for p in pos if 0 <= p < S)
+
+
+def _train_base(g, B, H, Hkv, S, D, vstep):
+    """Random +-0.25 keys, distinct v rows on multiples of 1/vstep in [1, 2),
+    integer do in [-4, 4].  fp64."""
+    k = 0.25 * (torch.randint(0, 2, (B, Hkv, S, D), generator=g) * 2.0 - 1.0)
+    v = 1.0 + torch.randint(0, vstep, (B, Hkv, S, D), generator=g) / vstep
+    j = torch.arange(S)
+    v[:, :, :, 0] = 1.0 + (j % vstep) / vstep              # distinct per key
+    v[:, :, :, 1] = 1.0 + (j // vstep) / vstep
+    v[:, :, :, 2] = 1.0 + (torch.arange(Hkv)[:, None] % vstep) / vstep
+    do = torch.randint(-4, 5, (B, H, S, D), generator=g).double()
+    return k.double(), v.double(), do
+
+
+def _pick(cands, count, cap):
+    """Least-used candidate (ties: first); None if all are at the cap."""
+    best = min(cands, key=lambda t: count[t])
+    return best if count[best] < cap else None
+
+
+def train_needle_input(tag, B, H, Hkv, S, D, causal):
+    """One target key per query row.  Returns a dict with q, do (B,H,S,D),
+    k, v (B,Hkv,S,D) in bf16, ``target`` (B,H,S) long, ``o_want`` bf16 and
+    ``dv_want`` (B,Hkv,S,D) fp64, kind = "needle".
+
+    Per (batch row, kv head) at most D-1 target keys: key 0 always, the rest
+    on both sides of every multiple of 32 (hence 64) plus keys 1, S-2, S-1,
+    the window rotated per (batch row, kv head) when there are more than fit.
+    Rows are dealt to targets 32-row q-tile by q-tile: a row that is itself a
+    target position takes it (the diagonal, which sits on both sides of every
+    q-tile edge); then, from the last row of the tile backwards and rotating
+    through the q-heads of the kv head, one row goes to each 32-key tile the
+    mask allows and the tile has not reached yet (to its least-used target);
+    every other row goes to the least-used target it can see.  A q-tile with
+    at least as many free rows as key tiles therefore reaches every key tile
+    it may see (asserted); a ragged last one reaches as many as it can.
+    No target is chosen by more than 31 * rep rows of its kv head
+    (rep = H / Hkv q-heads share it), asserted.  A cap of 31 per kv head,
+    which would keep |sum of do| <= 124 < 256 by counting alone, cannot be
+    met: under a causal mask rows 0..62 see only keys 0, 1, 31 and 32, which
+    is 63 rows per q-head for 4 targets.  What such a cap is for, that the
+    sum of do at every key is a bf16 number both per q-head (the kernel's
+    partial) and after the GQA sum, is therefore asserted on the sums
+    themselves (``_train_finish``)."""
+    g = _gen("train_needle", tag, B, H, Hkv, S, D, causal)
+    rep = H // Hkv
+    W = _walsh(D)
+    k, v, do = _train_base(g, B, H, Hkv, S, D, 128)
+    q = torch.empty(B, H, S, D, dtype=torch.float64)
+    target = torch.empty(B, H, S, dtype=torch.long)
+    cand = _train_candidates(S)
+    cap = 31 * rep
+    T = TRAIN_EDGE
+    for b in range(B):
+        for hk in range(Hkv):
+            if len(cand) > D - 1:
+                rest = [c for c in cand if c != 0]
+                r0 = ((b * Hkv + hk) * (D - 2)) % len(rest)
+                rest = (rest + rest)[r0:r0 + D - 2]
+                tg = [0] + sorted(rest)
+            else:
+                tg = cand
+            pat = {t: 1 + n for n, t in enumerate(tg)}
+            for t in tg:
+                k[b, hk, t] = 4.0 * W[pat[t]]
+            by_tile = {}
+            for t in tg:
+                by_tile.setdefault(t // T, []).append(t)
+            count = {t: 0 for t in tg}
+            covered = set()
+
+            def assign(h, i, t):
+                count[t] += 1
+                covered.add((i // T, t // T))
+                target[b, h, i] = t
+                q[b, h, i] = W[pat[t]]
+
+            for i0 in range(0, S, T):
+                rows = range(i0, min(S, i0 + T))
+                qt = i0 // T
+                tiles = [kt for kt in sorted(by_tile)
+                         if not causal or kt * T <= rows[-1]]
+                slots = []
+                for i in rows:
+                    for gq in range(rep):
+                        h = hk * rep + (gq + qt + b) % rep
+                        if i in pat and count[i] < cap:     # the diagonal
+                            assign(h, i, i)
+                        else:
+                            slots.append((h, i))
+                duty = [kt for kt in tiles if (qt, kt) not in covered]
+                for n, (h, i) in enumerate(slots[::-1]):
+                    vis = [t for t in tg if not causal or t <= i]
+                    t = None
+                    if n < len(duty):
+                        c = [x for x in by_tile[duty[n]] if x in vis]
+                        t = _pick(c, count, cap) if c else None
+                    if t is None:
+                        t = _pick(vis, count, cap + 1)
+                    assign(h, i, t)
+                if len(slots) >= len(tiles):
+                    for kt in tiles:
+                        assert (qt, kt) in covered, (tag, qt, kt)
+            assert max(count.values()) <= cap, (tag, max(count.values()), cap)
+    return _train_finish("needle", q, k, v, do, target, None, rep)
+
+
+def _tie_pairs(S, gap):
+    """(a, a + gap) key pairs with all positions distinct: one starting at
+    key 0, one ending on the last key, a = 1..3 and the last key of every
+    32-key tile, whose
+    partner is the first key of a tile two further on."""
+    want = [0, S - 1 - gap, 1, 2, 3] + \
+        list(range(TRAIN_EDGE - 1, S, TRAIN_EDGE))
+    used, pairs = set(), []
+    for a in want:
+        if a < 0 or a + gap >= S or a in used or a + gap in used:
+            continue
+        used |= {a, a + gap}
+        pairs.append((a, a + gap))
+    return sorted(pairs)
+
+
+def train_tie_input(tag, B, H, Hkv, S, D, causal):
+    """Like ``train_needle_input``, but pattern p < D/2 - 1 has two keys
+    4*W[1+p] +- 2*W[D/2+p], 65 keys apart (S // 2 when S < 130, so that short
+    sequences have pairs at all), both scoring exactly 4*sqrt(D).  A row that
+    sees both keys of its pair must return (v_a + v_b) / 2; a causal row
+    that sees only the first key (which only happens before its partner, at
+    the start of the sequence for the pair at key 0) is a single-needle row
+    on that key.  ``target`` is (B,H,S,2) with -1 for an unseen partner."""
+    g = _gen("train_tie", tag, B, H, Hkv, S, D, causal)
+    rep = H // Hkv
+    W = _walsh(D)
+    k, v, do = _train_base(g, B, H, Hkv, S, D, 64)
+    q = torch.empty(B, H, S, D, dtype=torch.float64)
+    target = torch.full((B, H, S, 2), -1, dtype=torch.long)
+    gap = TRAIN_TIE_GAP if S >= 2 * TRAIN_TIE_GAP else max(1, S // 2)
+    allp = _tie_pairs(S, gap) if S > 1 else []
+    npat = D // 2 - 1
+    for b in range(B):
+        for hk in range(Hkv):
+            if len(allp) > npat:
+                r0 = ((b * Hkv + hk) * npat) % len(allp)
+                pairs = sorted((allp + allp)[r0:r0 + npat])
+                if (0, gap) not in pairs:
+                    pairs[0] = (0, gap)
+            else:
+                pairs = allp
+            if not pairs:                  # S = 1: a single needle at key 0
+                k[b, hk, 0] = 4.0 * W[1]
+                q[b, hk * rep:(hk + 1) * rep] = W[1]
+                target[b, hk * rep:(hk + 1) * rep, :, 0] = 0
+                continue
+            for p, (a, c) in enumerate(pairs):
+                k[b, hk, a] = 4.0 * W[1 + p] + 2.0 * W[D // 2 + p]
+                k[b, hk, c] = 4.0 * W[1 + p] - 2.0 * W[D // 2 + p]
+            ends = {c: p for p, (a, c) in enumerate(pairs)}
+            starts = {a: p for p, (a, c) in enumerate(pairs)}
+            count = {p: 0 for p in range(len(pairs))}
+            for gq in range(rep):
+                h = hk * rep + gq
+                for i in range(S):
+                    both = [p for p, (a, c) in enumerate(pairs)
+                            if not causal or c <= i]
+                    if both:
+                        p = ends[i] if i in ends else \
+                            _pick(both[(i + gq) % len(both):] +
+                                  both[:(i + gq) % len(both)], count, 1 << 30)
+                        target[b, h, i, 1] = pairs[p][1]
+                    else:
+                        one = [p for p, (a, c) in enumerate(pairs) if a <= i]
+                        assert one, "key 0 starts a pair"
+                        p = starts[i] if i in starts else \
+                            _pick(one, count, 1 << 30)
+                    count[p] += 1
+                    target[b, h, i, 0] = pairs[p][0]
+                    q[b, h, i] = W[1 + p]
+    return _train_finish("tie", q, k, v, do, target[..., 0], target[..., 1],
+                         rep)
+
+
+def _train_finish(kind, q, k, v, do, ta, tb, rep):
+    B, H, S, D = q.shape
+    Hkv = H // rep
+    bf = torch.bfloat16
+    for t in (q, k, v, do):
+        assert torch.equal(t.to(bf).double(), t), "inputs are bf16 numbers"
+    hk = (torch.arange(H) // rep)[None, :, None].expand(B, H, S)
+    bb = torch.arange(B)[:, None, None].expand(B, H, S)
+    o = v[bb, hk, ta]
+    w = torch.ones(B, H, S, 1, dtype=torch.float64)
+    if tb is not None:
+        two = tb >= 0
+        o = torch.where(two[..., None], (o + v[bb, hk, tb.clamp_min(0)]) / 2, o)
+        w = torch.where(two[..., None], 0.5 * w, w)
+    dvh = torch.zeros(B, H, S, D, dtype=torch.float64)     # per q-head
+    hh = torch.arange(H)[None, :, None].expand(B, H, S)
+    dvh.index_put_((bb, hh, ta), w * do, accumulate=True)
+    if tb is not None:
+        sel = tb >= 0
+        dvh.index_put_((bb[sel], hh[sel], tb[sel]), (w * do)[sel],
+                       accumulate=True)
+    dv = dvh.view(B, Hkv, rep, S, D).sum(2)
+    assert torch.equal(o.to(bf).double(), o), "expected o is a bf16 number"
+    assert torch.equal(dvh.to(bf).double(), dvh), \
+        "per-head sum of do is a bf16 number"
+    assert torch.equal(dv.to(bf).double(), dv), "sum of do is a bf16 number"
+    target = ta if tb is None else torch.stack([ta, tb], -1)
+    return dict(kind=kind, q=q.to(bf), k=k.to(bf), v=v.to(bf), do=do.to(bf),
+                target=target, o_want=o.to(bf), dv_want=dv)
+
+
+def attn_ref64(q, k, v, do, causal, scale):
+    """fp64 attention forward and backward on the CPU with the per-element
+    magnitudes the tie check needs.  Returns a dict of o, lse, dq, dk, dv,
+    mag_dq = |dS| @ |k| and mag_dk = |dS|^T @ |q| summed over the q-heads of
+    a kv head."""
+    q, k, v, do = (t.detach().double().cpu() for t in (q, k, v, do))
+    B, H, S, D = q.shape
+    Hkv = k.shape[1]
+    rep = H // Hkv
+    ke = k.repeat_interleave(rep, 1)
+    ve = v.repeat_interleave(rep, 1)
+    s = _attn_scores(q, k, causal, scale)
+    lse = torch.logsumexp(s, -1)
+    p = torch.exp(s - lse.unsqueeze(-1))
+    o = p @ ve
+    dp = do @ ve.transpose(-1, -2)
+    delta = (do * o).sum(-1, keepdim=True)
+    ds = p * (dp - delta) * scale
+
+    def fold(t):
+        return t.view(B, Hkv, rep, S, D).sum(2)
+
+    return dict(o=o, lse=lse, dq=ds @ ke, dk=fold(ds.transpose(-1, -2) @ q),
+                dv=fold(p.transpose(-1, -2) @ do),
+                mag_dq=ds.abs() @ ke.abs(),
+                mag_dk=fold(ds.abs().transpose(-1, -2) @ q.abs()))
+
+
+def _worst(err, bound, what, fails):
+    """Print the worst element of err against bound; append a message to
+    ``fails`` if it exceeds it.  Returns max err."""
+    err = err.detach().double().cpu()
+    if not torch.isfinite(err).all():
+        fails.append(f"{what}: result is not finite")
+        return math.inf
+    i = int((err - bound).argmax())
+    idx = tuple(int(x) for x in torch.unravel_index(torch.tensor(i),
+                                                    err.shape))
+    e = float(err.flatten()[i])
+    bd = float(bound.flatten()[i]) if torch.is_tensor(bound) else float(bound)
+    print(f"NUMERICS {what}: max|err|={float(err.max()):.3e} "
+          f"worst err/bound={e:.3e}/{bd:.3e} at {idx}")
+    if not e <= bd:
+        fails.append(f"{what}: |err|={e:.3e} > bound {bd:.3e} at {idx}")
+    return float(err.max())
+
+
+def check_train_case(got, case, causal, what, ref=None):
+    """``got``: dict of o, dq, dk, dv (bf16) and lse (fp32) from the code
+    under test on a ``train_needle_input`` / ``train_tie_input`` case.
+
+    o: bit for bit.  lse: within FLOOR_LSE of fp64.  Needle: dv within 2**-24
+    of the sum of do, |dq|, |dk| <= 2**-20.  Tie: dv within 2**-20 of fp64
+    (which is a bf16 number up to e**-30 terms) and, per element,
+    |dq - fp64| <= 2**-7 * mag + 2**-20 (same for dk) with mag the sum of the
+    absolute values of the element's terms; 2**-7 = FLOOR_BF16_GRAD covers
+    three bf16 roundings of 2**-9 each (the dS operand, the output, and the
+    GQA partial sum or the dS workspace), the 2**-20 term the rows whose
+    do . (v_a - v_b) is exactly 0, where mag is 1e-12 and only noise is left.
+
+    Every quantity is checked before anything is raised, so one miss does
+    not hide the others; the AssertionError names each as "<what> <name>:".
+    Returns the worst dq and dk error over (mag + 2**-13) for a tie case."""
+    D = case["q"].shape[-1]
+    scale = 1.0 / math.sqrt(D)
+    if ref is None:
+        ref = attn_ref64(case["q"], case["k"], case["v"], case["do"], causal,
+                         scale)
+    fails = []
+    for n in ("o", "dq", "dk", "dv"):
+        assert got[n].dtype == torch.bfloat16, f"{what} {n}: {got[n].dtype}"
+        assert got[n].shape == ref[n].shape, f"{what} {n}: {got[n].shape}"
+    try:
+        check_needles(got["o"], case["o_want"], what + " o")
+    except AssertionError as e:
+        fails.append(str(e))
+    _worst((got["lse"].double().cpu() - ref["lse"]).abs(), FLOOR_LSE,
+           what + " lse", fails)
+    g = {n: got[n].detach().double().cpu() for n in ("dq", "dk", "dv")}
+    out = None
+    if case["kind"] == "needle":
+        _worst((g["dv"] - case["dv_want"]).abs(), BOUND_TRAIN_DV,
+               what + " dv", fails)
+        _worst(g["dq"].abs(), BOUND_TRAIN_ZERO, what + " dq", fails)
+        _worst(g["dk"].abs(), BOUND_TRAIN_ZERO, what + " dk", fails)
+    else:
+        _worst((g["dv"] - ref["dv"]).abs(), BOUND_TRAIN_ZERO, what + " dv",
+               fails)
+        out = []
+        for n in ("dq", "dk"):
+            err, mag = (g[n] - ref[n]).abs(), ref["mag_" + n]
+            _worst(err, FLOOR_BF16_GRAD * mag + BOUND_TRAIN_ZERO,
+                   f"{what} {n}", fails)
+            out.append(float((err / (mag + 2.0 ** -13)).max()))
+        out = tuple(out)
+    assert not fails, "; ".join(fails)
+    return out
+
+
+def _saved_lse(t):
+    """lse as saved by the attention autograd function that produced ``t``
+    (every one of them saves it last), found through views and reshapes."""
+    todo, seen = [t.grad_fn], set()
+    while todo:
+        n = todo.pop()
+        if n is None or n in seen:
+            continue
+        seen.add(n)
+        if hasattr(n, "saved_tensors"):
+            return n.saved_tensors[-1].detach()
+        todo.extend(f for f, _ in n.next_functions)
+    raise AssertionError("no attention function in the graph")
+
+
+def run_attention(fn, case, device):
+    """o, lse, dq, dk, dv of ``fn(q, k, v)`` -> (B,H,S,D) on a case's
+    inputs (or on a (q, k, v, do) tuple)."""
+    if not isinstance(case, dict):
+        case = dict(zip(("q", "k", "v", "do"), case))
+    q, k, v = (case[n].to(device).requires_grad_(True) for n in "qkv")
+    o = fn(q, k, v)
+    lse = _saved_lse(o)
+    o.backward(case["do"].to(device))
+    return dict(o=o.detach(), lse=lse, dq=q.grad, dk=k.grad, dv=v.grad)
+
+
+def _sbh(t):
+    """(B, H, S, D) -> contiguous (S, B, H*D)."""
+    B, H, S, D = t.shape
+    return t.permute(2, 0, 1, 3).reshape(S, B, H * D).contiguous()
+
+
+def _bhsd(t, H):
+    """(S, B, H*D) -> (B, H, S, D) view."""
+    S, B, HD = t.shape
+    return t.view(S, B, H, HD // H).permute(1, 2, 0, 3)
+
+
+def run_fused_qkv(fn, case, device, causal):
+    """The case through ``fn`` = ops.fused_qkv_attention: qkv is built as
+    (S, B, 3*H*hd) from the case's q, k, v (H == Hkv), dqkv is split back.
+    Also returns the raw ``dqkv`` (every element of which is a gradient)."""
+    if not isinstance(case, dict):
+        case = dict(zip(("q", "k", "v", "do"), case))
+    H = case["q"].shape[1]
+    assert case["k"].shape[1] == H
+    qkv = torch.cat([_sbh(case[n]) for n in "qkv"], -1).to(device)
+    qkv.requires_grad_(True)
+    o = fn(qkv, H, causal=causal)
+    lse = _saved_lse(o)
+    o.backward(_sbh(case["do"]).to(device))
+    dq, dk, dv = (_bhsd(g.contiguous(), H)
+                  for g in qkv.grad.chunk(3, -1))
+    return dict(o=_bhsd(o.detach(), H), lse=lse, dq=dq, dk=dk, dv=dv,
+                dqkv=qkv.grad)
+
+
+def run_gqa(fn, case, device, causal):
+    """The case through ``fn`` = ops.gqa_attention with v a strided view of
+    an (S, B, Hkv*hd) buffer, as the Llama block passes it."""
+    if not isinstance(case, dict):
+        case = dict(zip(("q", "k", "v", "do"), case))
+    H, Hkv = case["q"].shape[1], case["k"].shape[1]
+    q, k = (case[n].to(device).requires_grad_(True) for n in "qk")
+    vbuf = _sbh(case["v"]).to(device).requires_grad_(True)
+    o = fn(q, k, _bhsd(vbuf, Hkv), causal=causal)
+    lse = _saved_lse(o)
+    o.backward(_sbh(case["do"]).to(device))
+    return dict(o=_bhsd(o.detach(), H), lse=lse, dq=q.grad, dk=k.grad,
+                dv=_bhsd(vbuf.grad, Hkv))
+
+
+def run_ring_blocks(case, nblk, device):
+    """Causal ring attention's block math on one device: the sequence is cut
+    into ``nblk`` blocks, query block r runs ring._fwd_partial against key
+    blocks r (causal), r-1, ..., 0 (full) in ring order and merges them with
+    ring._merge_partials, then ring._bwd_partial per block with the merged o
+    and the global lse, accumulating in fp32 as _RingAttention does."""
+    from torchdistpackage_amd.parallel.context import ring
+    if not isinstance(case, dict):
+        case = dict(zip(("q", "k", "v", "do"), case))
+    q, k, v, do = (case[n].to(device) for n in ("q", "k", "v", "do"))
+    B, H, S, D = q.shape
+    assert k.shape[1] == H and S % nblk == 0
+    L = S // nblk
+    scale = 1.0 / math.sqrt(D)
+    blk = lambda t, r: t[:, :, r * L:(r + 1) * L].contiguous()  # noqa: E731
+    o, lse = torch.empty_like(q), torch.empty(B, H, S, device=device)
+    dq = torch.empty_like(q)
+    dk = torch.zeros(B, H, S, D, dtype=torch.float32, device=device)
+    dv = torch.zeros_like(dk)
+    with torch.no_grad():
+        for r in range(nblk):
+            qr, o_acc, lse_acc = blk(q, r), None, None
+            for src in range(r, -1, -1):
+                o_p, lse_p = ring._fwd_partial(qr, blk(k, src), blk(v, src),
+                                               src == r, scale)
+                if o_acc is None:
+                    o_acc, lse_acc = o_p, lse_p
+                else:
+                    o_acc, lse_acc = ring._merge_partials(o_acc, lse_acc,
+                                                          o_p, lse_p)
+            o[:, :, r * L:(r + 1) * L] = o_acc
+            lse[:, :, r * L:(r + 1) * L] = lse_acc
+            dq_acc = torch.zeros_like(qr, dtype=torch.float32)
+            for src in range(r, -1, -1):
+                dq_p, dk_p, dv_p = ring._bwd_partial(
+                    blk(do, r), qr, blk(k, src), blk(v, src), o_acc, lse_acc,
+                    src == r, scale)
+                dq_acc += dq_p.float()
+                dk[:, :, src * L:(src + 1) * L] += dk_p.float()
+                dv[:, :, src * L:(src + 1) * L] += dv_p.float()
+            dq[:, :, r * L:(r + 1) * L] = dq_acc.to(q.dtype)
+    return dict(o=o, lse=lse, dq=dq, dk=dk.to(q.dtype), dv=dv.to(q.dtype))
+
+
+def rows_reaching_other_blocks(case, L):
+    """Number of rows whose target (or either key of whose pair) lies in
+    another block of L keys than the row itself."""
+    t = case["target"]
+    B, H, S = t.shape[:3]
+    t = t.reshape(B, H, S, -1)
+    own = (torch.arange(S) // L)[None, None, :, None]
+    return int(((t >= 0) & (t // L != own)).any(-1).sum())
+
+
+def attn_yardstick(got, tensors, causal, device, what, tiny=None):
+    """o, dq, dk, dv of ``got`` against the fp64 eager chain with the bf16
+    eager chain on ``device`` as the yardstick, exactly as check_fwd_bwd
+    does for test_flash_attention.  Returns {name: (e_got, e_lib)}."""
+    q, k, v, do = tensors
+    scale = 1.0 / math.sqrt(q.shape[-1])
+    fn = lambda q, k, v: attn_chain(q, k, v, causal, scale)  # noqa: E731
+    y_ref, g_ref = fwd_bwd(fn, (q, k, v), do, torch.float64, "cpu")
+    y_lib, g_lib = fwd_bwd(fn, (q, k, v), do, torch.bfloat16, device)
+    tiny = tiny or {}
+    out = {"o": yardstick(got["o"], y_ref, y_lib, FLOOR_BF16_FWD,
+                          what=f"{what} y")}
+    for n, gr, gl in zip("qkv", g_ref, g_lib):
+        out["d" + n] = yardstick(got["d" + n], gr, gl, FLOOR_BF16_GRAD,
+                                 tiny=tiny.get(n, TINY), what=f"{what} d{n}")
+    return out
+
+
+ATTN_SHAPES_TILED = [      # (B, H, Hkv, S, D): more than one tile everywhere
+    (1, 2, 2, 300, 64),
+    (1, 4, 1, 257, 64),
+    (1, 2, 2, 300, 128),
+    (2, 4, 2, 520, 128),
+]
+TRAIN_S = [33, 256, 257, 300, 520]
+TRAIN_HEADS = [(1, 2, 2), (2, 4, 2), (1, 4, 1)]          # (B, H, Hkv)
+
+# knobs of ops.attention_route per head-dim-128 route; head dim 64 has one
+ATTN_ROUTES = {
+    "default": {},
+    "recompute": {"dq_recompute": True},
+    "over_budget": {"max_ds_bytes": 0},
+    "no_tr16": {"no_tr16": True},
+    "pstore": {"pstore": True},
+    "v1": {"force_v1": True},
+}

@@ -15,6 +15,7 @@ Dispatch policy:
 
 from __future__ import annotations
 
+import contextlib
 import math
 import os
 from typing import Optional
@@ -312,6 +313,35 @@ class _FlashAttentionFn(torch.autograd.Function):
                 dv = dv.view(B, Hkv, rep, S, D).sum(2)
             dq, dk, dv = dq.to(q.dtype), dk.to(k.dtype), dv.to(v.dtype)
         return dq, dk, dv, None, None
+
+
+_ATTN_KNOBS = ("dq_recompute", "no_tr16", "pstore", "force_v1",
+               "max_ds_bytes")
+
+
+def attention_knobs() -> dict:
+    """The run-time switches of the attention dispatch (docs/knobs.md)."""
+    return dict(zip(_ATTN_KNOBS, ext("attention_knobs").attn_knobs()))
+
+
+@contextlib.contextmanager
+def attention_route(**knobs):
+    """Run the body with some attention knobs replaced, e.g.
+    ``attention_route(dq_recompute=True)`` or ``attention_route(
+    max_ds_bytes=0)``; the previous values come back on exit.  Process-wide
+    and not thread-safe: meant for tests and A/B runs."""
+    unknown = set(knobs) - set(_ATTN_KNOBS)
+    if unknown:
+        raise TypeError(f"unknown attention knob(s) {sorted(unknown)}; "
+                        f"known: {_ATTN_KNOBS}")
+    e = ext("attention_knobs")
+    cur = attention_knobs()
+    cur.update(knobs)
+    prev = e.attn_set_knobs(*(cur[n] for n in _ATTN_KNOBS))
+    try:
+        yield
+    finally:
+        e.attn_set_knobs(*prev)
 
 
 _warned_hd = set()

@@ -26,7 +26,10 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 #include "common.h"
+#include "attn_knobs.h"
 #include <cstdlib>
+#include <string>
+#include <tuple>
 
 namespace {
 
@@ -557,7 +560,9 @@ __global__ void attn_bwd_dkdv_kernel(const unsigned short* __restrict__ q,
         float p = valid ?
             __expf(st_acc[qg][rr] * scale - lse_lds[qg * 16 + l15]) : 0.f;
         st_acc[qg][rr] = p;
-        stw[swz32(lg * 4 + rr, qg * 16 + l15)] = f2bf(p);
+        // the dv MFMA gets an exact 0 for a negligible P (attn_knobs.h)
+        stw[swz32(lg * 4 + rr, qg * 16 + l15)] =
+            f2bf(p < kAttnPFlush ? 0.f : p);
       }
     }
 
@@ -608,7 +613,104 @@ Strides get_strides(const torch::Tensor& t) {
   return Strides{t.stride(0), t.stride(1), t.stride(2)};
 }
 
+// Every kernel here and in attention_v2.hip reads its bf16 operands as
+// 8-element vectors (pack8 / pack8v: one 16-byte load per lane) at
+// base + b*stride_b + h*stride_h + s*stride_s + 8*i, and the v2 kernels write
+// o and dq as 4-element vectors, so the base address must be 16-byte aligned
+// and the batch/head/row strides multiples of 8 elements.  Nothing in the
+// kernels checks a shape: a short v, o or gradient buffer is read or written
+// out of bounds.  Everything is therefore checked here, before any launch.
+void check_operand(const char* fn, const char* name, const torch::Tensor& t,
+                   const torch::Tensor& q, int64_t B, int64_t Hh, int64_t S,
+                   int64_t D) {
+  TORCH_CHECK(t.is_cuda() && t.device() == q.device(), fn, ": ", name,
+              " must be on q's device ", q.device(), ", got ", t.device());
+  TORCH_CHECK(t.scalar_type() == torch::kBFloat16, fn, ": ", name,
+              " must be bf16, got ", t.scalar_type());
+  TORCH_CHECK(t.dim() == 4 && t.size(0) == B && t.size(1) == Hh &&
+                  t.size(2) == S && t.size(3) == D,
+              fn, ": ", name, " must be (", B, ", ", Hh, ", ", S, ", ", D,
+              "), got ", t.sizes());
+  TORCH_CHECK(t.stride(3) == 1, fn, ": ", name,
+              " must have a contiguous last dim, got stride ", t.stride(3));
+  for (int d = 0; d < 3; ++d)
+    TORCH_CHECK(t.size(d) == 1 || t.stride(d) % 8 == 0, fn, ": ", name,
+                " stride ", t.stride(d), " of dim ", d, " is not a multiple "
+                "of 8 elements: the kernels use 16-byte vector accesses");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, fn, ": ",
+              name, " is not 16-byte aligned: the kernels use 16-byte vector "
+              "accesses");
+}
+
+// Returns (B, H, Hkv, S, D) after checking q, k, v.
+std::tuple<int64_t, int64_t, int64_t, int64_t, int64_t> check_qkv(
+    const char* fn, const torch::Tensor& q, const torch::Tensor& k,
+    const torch::Tensor& v) {
+  TORCH_CHECK(q.is_cuda() && q.scalar_type() == torch::kBFloat16, fn,
+              ": bf16 CUDA tensors required");
+  TORCH_CHECK(q.dim() == 4, fn, ": q must be (B, H, S, D), got ", q.sizes());
+  const int64_t B = q.size(0), H = q.size(1), S = q.size(2), D = q.size(3);
+  TORCH_CHECK(D == 64 || D == 128, fn, ": head_dim must be 64 or 128, got ",
+              D);
+  TORCH_CHECK(B >= 1 && H >= 1 && S >= 1, fn,
+              ": empty problem (S = 0?), q is ", q.sizes());
+  TORCH_CHECK(k.dim() == 4 && v.dim() == 4, fn,
+              ": k and v must be (B, Hkv, S, D), got ", k.sizes(), " and ",
+              v.sizes());
+  const int64_t Hkv = k.size(1);
+  TORCH_CHECK(Hkv >= 1 && H % Hkv == 0, fn,
+              ": n_head must be a multiple of n_kv_head, got ", H, " and ",
+              Hkv);
+  TORCH_CHECK(k.size(2) == S, fn,
+              ": cross-attention S_kv != S_q not supported yet (k has ",
+              k.size(2), " keys, q ", S, " rows)");
+  check_operand(fn, "q", q, q, B, H, S, D);
+  check_operand(fn, "k", k, q, B, Hkv, S, D);
+  check_operand(fn, "v", v, q, B, Hkv, S, D);
+  return {B, H, Hkv, S, D};
+}
+
 }  // namespace
+
+AttnKnobs& attn_knobs_ref() {
+  static AttnKnobs k{
+      std::getenv("TDPA_DQ_RECOMPUTE") != nullptr,
+      std::getenv("TDPA_NO_TR16") != nullptr,
+      std::getenv("TDPA_PSTORE") != nullptr,
+      std::getenv("TDPA_ATTN_V1") != nullptr,
+      (int64_t)4 << 30};
+  return k;
+}
+
+using KnobTuple = std::tuple<bool, bool, bool, bool, int64_t>;
+
+// (dq_recompute, no_tr16, pstore, force_v1, max_ds_bytes)
+KnobTuple attn_knobs() {
+  const AttnKnobs& k = attn_knobs_ref();
+  return {k.dq_recompute, k.no_tr16, k.pstore, k.force_v1, k.max_ds_bytes};
+}
+
+// Replaces the knobs; returns the previous ones.
+KnobTuple attn_set_knobs(bool dq_recompute, bool no_tr16, bool pstore,
+                         bool force_v1, int64_t max_ds_bytes) {
+  KnobTuple prev = attn_knobs();
+  attn_knobs_ref() =
+      AttnKnobs{dq_recompute, no_tr16, pstore, force_v1, max_ds_bytes};
+  return prev;
+}
+
+// Name of what attn_bwd_select gives a (B, H, S, D) problem under the
+// current knobs, the struct attn_bwd dispatches on: "v1", "v2_recompute", or
+// "v2_workspace" with "+pstore" / "+no_tr16" appended.
+std::string attn_bwd_route(int64_t B, int64_t H, int64_t S, int64_t D) {
+  const AttnBwdRoute r = attn_bwd_select(attn_knobs_ref(), B, H, S, D);
+  if (r.v1) return "v1";
+  if (r.recompute) return "v2_recompute";
+  std::string name = "v2_workspace";
+  if (r.pstore) name += "+pstore";
+  if (r.no_tr16) name += "+no_tr16";
+  return name;
+}
 
 void attn_fwd_v2(torch::Tensor q, torch::Tensor k, torch::Tensor v,
                  torch::Tensor o, torch::Tensor lse, bool causal,
@@ -619,7 +721,7 @@ void attn_bwd_dq_v2(torch::Tensor dout, torch::Tensor q, torch::Tensor k,
 void attn_bwd_v2_all(torch::Tensor dout, torch::Tensor q, torch::Tensor k,
                      torch::Tensor v, torch::Tensor lse, torch::Tensor delta,
                      torch::Tensor dq, torch::Tensor dk, torch::Tensor dv,
-                     bool causal, double scale);
+                     bool causal, double scale, const AttnBwdRoute& route);
 void attn_bwd_dkdv_v2(torch::Tensor dout, torch::Tensor q, torch::Tensor k,
                       torch::Tensor v, torch::Tensor lse, torch::Tensor delta,
                       torch::Tensor dk, torch::Tensor dv, bool causal,
@@ -628,16 +730,12 @@ void attn_bwd_dkdv_v2(torch::Tensor dout, torch::Tensor q, torch::Tensor k,
 std::vector<torch::Tensor> attn_fwd(torch::Tensor q, torch::Tensor k,
                                     torch::Tensor v, torch::Tensor o,
                                     bool causal, double scale) {
-  TORCH_CHECK(q.is_cuda() && q.scalar_type() == torch::kBFloat16,
-              "attn_fwd: bf16 CUDA tensors required");
-  const int B = q.size(0), H = q.size(1), S = q.size(2), D = q.size(3);
-  const int Hkv = k.size(1);
-  TORCH_CHECK(H % Hkv == 0, "n_head must be a multiple of n_kv_head");
+  auto [B_, H_, Hkv_, S_, D_] = check_qkv("attn_fwd", q, k, v);
+  check_operand("attn_fwd", "o", o, q, B_, H_, S_, D_);
+  const int B = B_, H = H_, S = S_, D = D_, Hkv = Hkv_;
   const int q_per_kv = H / Hkv;
-  TORCH_CHECK(k.size(2) == S, "cross-attention S_kv != S_q not supported yet");
-  TORCH_CHECK(D == 64 || D == 128, "head_dim must be 64 or 128");
   auto lse = torch::empty({B, H, S}, q.options().dtype(torch::kFloat));
-  static const bool force_v1 = std::getenv("TDPA_ATTN_V1") != nullptr;
+  const bool force_v1 = attn_knobs_ref().force_v1;
   if (D == 128 && !force_v1) {
     attn_fwd_v2(q, k, v, o, lse, causal, scale);
     return {o, lse};
@@ -669,16 +767,27 @@ std::vector<torch::Tensor> attn_bwd(torch::Tensor dout, torch::Tensor q,
                                     torch::Tensor dq, torch::Tensor dk,
                                     torch::Tensor dv,
                                     bool causal, double scale) {
-  TORCH_CHECK(q.is_cuda() && q.scalar_type() == torch::kBFloat16);
-  const int B = q.size(0), H = q.size(1), S = q.size(2), D = q.size(3);
-  const int Hkv = k.size(1);
-  TORCH_CHECK(H % Hkv == 0);
+  auto [B_, H_, Hkv_, S_, D_] = check_qkv("attn_bwd", q, k, v);
+  const int B = B_, H = H_, S = S_, D = D_, Hkv = Hkv_;
   const int q_per_kv = H / Hkv;
+  check_operand("attn_bwd", "dout", dout, q, B, H, S, D);
+  check_operand("attn_bwd", "o", o, q, B, H, S, D);
+  check_operand("attn_bwd", "dq", dq, q, B, H, S, D);
   // GQA: dk/dv buffers must be per-Q-HEAD partials (B,H,S,D); the wrapper
   // sums groups of q_per_kv afterwards
-  TORCH_CHECK(dk.size(1) == H && dv.size(1) == H,
-              "dk/dv must be expanded to H q-heads for GQA");
-  TORCH_CHECK(D == 64 || D == 128);
+  TORCH_CHECK(dk.dim() == 4 && dv.dim() == 4 && dk.size(1) == H &&
+                  dv.size(1) == H,
+              "attn_bwd: dk/dv must be expanded to H q-heads for GQA, got ",
+              dk.sizes(), " and ", dv.sizes(), " for H = ", H);
+  check_operand("attn_bwd", "dk", dk, q, B, H, S, D);
+  check_operand("attn_bwd", "dv", dv, q, B, H, S, D);
+  TORCH_CHECK(lse.is_cuda() && lse.device() == q.device() &&
+                  lse.scalar_type() == torch::kFloat && lse.dim() == 3 &&
+                  lse.size(0) == B && lse.size(1) == H && lse.size(2) == S &&
+                  lse.is_contiguous(),
+              "attn_bwd: lse must be a contiguous fp32 (", B, ", ", H, ", ",
+              S, ") tensor on q's device, got ", lse.scalar_type(), " ",
+              lse.sizes(), " strides ", lse.strides(), " on ", lse.device());
   auto delta = torch::empty({B, H, S}, q.options().dtype(torch::kFloat));
   auto stream = at::cuda::getCurrentHIPStream();
   Strides qs = get_strides(q), ks = get_strides(k), vs = get_strides(v),
@@ -695,9 +804,10 @@ std::vector<torch::Tensor> attn_bwd(torch::Tensor dout, torch::Tensor q,
                        delta.data_ptr<float>(), os, dos, B, H, S, D);
   }
 
-  static const bool force_v1b = std::getenv("TDPA_ATTN_V1") != nullptr;
-  if (D == 128 && !force_v1b) {
-    attn_bwd_v2_all(dout, q, k, v, lse, delta, dq, dk, dv, causal, scale);
+  const AttnBwdRoute route = attn_bwd_select(attn_knobs_ref(), B, H, S, D);
+  if (!route.v1) {
+    attn_bwd_v2_all(dout, q, k, v, lse, delta, dq, dk, dv, causal, scale,
+                    route);
     HIP_CHECK_LAST();
     return {dq, dk, dv};
   }

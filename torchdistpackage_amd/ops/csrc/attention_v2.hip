@@ -18,6 +18,7 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 #include "common.h"
+#include "attn_knobs.h"
 
 namespace {
 
@@ -761,8 +762,12 @@ __global__ void attn_bwd_dkdv_v2_kernel(
           p = bf2f(((const unsigned short*)p_img)[r]);
         } else {
           bool valid = key < S && qrow < S && (!CAUSAL || key <= qrow);
-          p = valid ?
-              __expf(s_acc[r] * scale - lse_lds[buf][qrel]) : 0.f;
+          const float e = __expf(s_acc[r] * scale - lse_lds[buf][qrel]);
+          // the dv MFMA gets an exact 0 for a negligible P (attn_knobs.h),
+          // folded into the mask's select: one compare per element.  Under
+          // pstore (PMODE 1) this P is also what the dk pass reloads
+          if (!DK_PASS) valid = valid && !(e < kAttnPFlush);
+          p = valid ? e : 0.f;
         }
         s_acc[r] = DK_PASS
             ? p * (dp_acc[r] - del_lds[buf][qrel]) * scale : p;
@@ -1146,32 +1151,47 @@ __global__ void attn_bwd_dq_lite_tr_kernel(
 }
 
 }  // namespace
+
+// The one place that decides which backward kernels run (attn_knobs.h).
+// Head dim 64, or force_v1: the v1 pair.  Otherwise the no-workspace route
+// (attn_bwd_dq_v2 + attn_bwd_dkdv_v2) when asked for, or when the dS
+// workspace (twice as large with the P workspace of pstore) would exceed the
+// cap; else the workspace route, where pstore and no_tr16 apply.
+AttnBwdRoute attn_bwd_select(const AttnKnobs& knobs, int64_t B, int64_t H,
+                             int64_t S, int64_t D) {
+  AttnBwdRoute r{false, false, false, false};
+  r.v1 = D != 128 || knobs.force_v1;
+  if (r.v1) return r;
+  const int64_t spad_est = (S + QT2 - 1) / QT2 * QT2;
+  const int64_t pmul = knobs.pstore ? 4 : 2;
+  const int64_t ds_bytes = B * H * S * spad_est * pmul;
+  r.recompute = knobs.dq_recompute || ds_bytes > knobs.max_ds_bytes;
+  if (r.recompute) return r;
+  r.pstore = knobs.pstore;
+  r.no_tr16 = knobs.no_tr16;
+  return r;
+}
+
 // Combined backward: dv pass, dk pass storing dS, dq-lite consuming it.
-// TDPA_DQ_RECOMPUTE falls back to the independent recomputing dq kernel
+// route.recompute falls back to the independent recomputing dq kernel
 // (and no dS workspace) for A/B and as an escape hatch.
 void attn_bwd_v2_all(torch::Tensor dout, torch::Tensor q, torch::Tensor k,
                      torch::Tensor v, torch::Tensor lse, torch::Tensor delta,
                      torch::Tensor dq, torch::Tensor dk, torch::Tensor dv,
-                     bool causal, double scale) {
-  static const bool recompute = std::getenv("TDPA_DQ_RECOMPUTE") != nullptr;
+                     bool causal, double scale, const AttnBwdRoute& route) {
+  TORCH_CHECK(!route.v1, "attn_bwd_v2_all: the v1 route is attn_bwd's");
   // The dS-store path buys -13% backward time (r01 v12) at the cost of an
   // O(S^2) bf16 workspace (B*H*S*S_pad).  That grows quadratically with
   // sequence length (536 MB at the bench shape, ~8.6 GB at S=8192/B=16) —
-  // above a fixed budget switch to the recompute-dq path, which needs no
-  // workspace and loses only the 13% (bound the
-  // workspace for the long-context direction).
-  constexpr long kMaxDsBytes = 4L << 30;  // 4 GiB cap (S=4096/B=4 stays
-                                          // on the fast path, S>=8192 not)
-  {
-    const long Sq = q.size(2);
-    const long spad_est = (Sq + QT2 - 1) / QT2 * QT2;
-    const long pmul = std::getenv("TDPA_PSTORE") != nullptr ? 4 : 2;
-    const long ds_bytes = (long)q.size(0) * q.size(1) * Sq * spad_est * pmul;
-    if (recompute || ds_bytes > kMaxDsBytes) {
-      attn_bwd_dq_v2(dout, q, k, v, lse, delta, dq, causal, scale);
-      attn_bwd_dkdv_v2(dout, q, k, v, lse, delta, dk, dv, causal, scale);
-      return;
-    }
+  // above a fixed budget (AttnKnobs::max_ds_bytes, 4 GiB: S=4096/B=4 stays
+  // on the fast path, S>=8192 not) attn_bwd_select switches to the
+  // recompute-dq path, which needs no workspace and loses only the 13%
+  // (bound the workspace for the long-context
+  // direction).
+  if (route.recompute) {
+    attn_bwd_dq_v2(dout, q, k, v, lse, delta, dq, causal, scale);
+    attn_bwd_dkdv_v2(dout, q, k, v, lse, delta, dk, dv, causal, scale);
+    return;
   }
   const int B = q.size(0), H = q.size(1), S = q.size(2), D = q.size(3);
   const int Hkv = k.size(1);
@@ -1191,7 +1211,7 @@ void attn_bwd_v2_all(torch::Tensor dout, torch::Tensor q, torch::Tensor k,
   // ways): the saved MFMAs are repaid by the extra S^2 bf16 write+read —
   // kept for shapes where the balance may differ, default OFF so the
   // backward's workspace stays a single dS buffer.
-  static const bool pstore = std::getenv("TDPA_PSTORE") != nullptr;
+  const bool pstore = route.pstore;
   torch::Tensor pwt;
   unsigned short* pw = nullptr;
   if (pstore) {
@@ -1206,7 +1226,7 @@ void attn_bwd_v2_all(torch::Tensor dout, torch::Tensor q, torch::Tensor k,
     else L_KV2(false, true, dsp, spad, nullptr, 0, 0);
   }
 #undef L_KV2
-  static const bool no_tr16 = std::getenv("TDPA_NO_TR16") != nullptr;
+  const bool no_tr16 = route.no_tr16;
 #define L_DQL(CC)                                                             \
   do {                                                                        \
     if (no_tr16)                                                              \

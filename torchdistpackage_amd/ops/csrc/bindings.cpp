@@ -46,6 +46,11 @@ std::vector<torch::Tensor> attn_bwd(torch::Tensor dout, torch::Tensor q,
                                     torch::Tensor dq, torch::Tensor dk,
                                     torch::Tensor dv,
                                     bool causal, double scale);
+std::tuple<bool, bool, bool, bool, int64_t> attn_knobs();
+std::tuple<bool, bool, bool, bool, int64_t> attn_set_knobs(
+    bool dq_recompute, bool no_tr16, bool pstore, bool force_v1,
+    int64_t max_ds_bytes);
+std::string attn_bwd_route(int64_t B, int64_t H, int64_t S, int64_t D);
 torch::Tensor mfma_probe_16x16x32(torch::Tensor a, torch::Tensor b);
 torch::Tensor mfma_probe_32x32x16(torch::Tensor a, torch::Tensor b);
 torch::Tensor tr16_probe(long addr_mode);
@@ -93,6 +98,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("scale_inplace", &scale_inplace);
   m.def("attn_fwd", &attn_fwd);
   m.def("attn_bwd", &attn_bwd);
+  m.def("attn_knobs", &attn_knobs,
+        "(dq_recompute, no_tr16, pstore, force_v1, max_ds_bytes)");
+  m.def("attn_set_knobs", &attn_set_knobs,
+        "set the five attention knobs; returns the previous five");
+  m.def("attn_bwd_route", &attn_bwd_route,
+        "name of the backward route for (B, H, S, D) under the current knobs");
   m.def("mfma_probe_16x16x32", &mfma_probe_16x16x32);
   m.def("mfma_probe_32x32x16", &mfma_probe_32x32x16);
   m.def("tr16_probe", &tr16_probe);

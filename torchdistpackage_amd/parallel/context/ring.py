@@ -64,7 +64,9 @@ def _fwd_partial(q, k, v, causal, scale):
         _, lse = ext("flash_attention").attn_fwd(q, k, v, o, bool(causal),
                                                  float(scale))
         return o, lse
-    qf, kf, vf = q.float(), k.float(), v.float()
+    # CPU reference branch: fp64, so that exp(s - lse) in _bwd_partial is not
+    # limited by the fp32 spacing of s and lse (4e-6 at a score of 45)
+    qf, kf, vf = q.double(), k.double(), v.double()
     s = torch.matmul(qf, kf.transpose(-1, -2)) * scale
     if causal:
         S = q.shape[-2]
@@ -76,6 +78,16 @@ def _fwd_partial(q, k, v, causal, scale):
     return o, lse
 
 
+def _merge_partials(o_a, lse_a, o_b, lse_b):
+    """Merge two flash partials over disjoint key sets:
+    lse = logaddexp(lse_a, lse_b); o = o_a*exp(lse_a-lse) + o_b*exp(lse_b-lse)
+    (weights and products in o's dtype)."""
+    lse = torch.logaddexp(lse_a, lse_b)
+    w_a = torch.exp(lse_a - lse).unsqueeze(-1).to(o_b.dtype)
+    w_b = torch.exp(lse_b - lse).unsqueeze(-1).to(o_b.dtype)
+    return o_a * w_a + o_b * w_b, lse
+
+
 def _bwd_partial(do, q, k, v, o, lse, causal, scale):
     """(dq, dk, dv) of one block given the GLOBAL lse (and o for delta)."""
     if q.is_cuda:
@@ -85,15 +97,15 @@ def _bwd_partial(do, q, k, v, o, lse, causal, scale):
         ext("flash_attention").attn_bwd(do, q, k, v, o, lse, dq, dk, dv,
                                         bool(causal), float(scale))
         return dq, dk, dv
-    qf, kf, vf = q.float(), k.float(), v.float()
-    dof, of = do.float(), o.float()
+    qf, kf, vf = q.double(), k.double(), v.double()
+    dof, of = do.double(), o.double()
     s = torch.matmul(qf, kf.transpose(-1, -2)) * scale
     if causal:
         S = q.shape[-2]
         mask = torch.ones(S, k.shape[-2], dtype=torch.bool,
                           device=q.device).tril_()
         s = s.masked_fill(~mask, float("-inf"))
-    p = torch.exp(s - lse.unsqueeze(-1).float())
+    p = torch.exp(s - lse.unsqueeze(-1).double())
     dv = torch.matmul(p.transpose(-1, -2), dof)
     dp = torch.matmul(dof, vf.transpose(-1, -2))
     delta = (dof * of).sum(-1, keepdim=True)
@@ -135,13 +147,8 @@ class _RingAttention(torch.autograd.Function):
                     if o_acc is None:
                         o_acc, lse_acc = o_p, lse_p
                     else:
-                        new_lse = torch.logaddexp(lse_acc, lse_p)
-                        w_a = torch.exp(lse_acc - new_lse) \
-                            .unsqueeze(-1).to(o_p.dtype)
-                        w_b = torch.exp(lse_p - new_lse) \
-                            .unsqueeze(-1).to(o_p.dtype)
-                        o_acc = o_acc * w_a + o_p * w_b
-                        lse_acc = new_lse
+                        o_acc, lse_acc = _merge_partials(
+                            o_acc, lse_acc, o_p, lse_p)
                 if works is not None:
                     _shift_end(works)
                     k_cur, k_nxt = k_nxt, k_cur
