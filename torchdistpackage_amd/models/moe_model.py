@@ -10,7 +10,8 @@ layer is in-package (moe/layer.py) and the swap is a config flag.
 
 from __future__ import annotations
 
-from dataclasses import dataclass
+import os
+from dataclasses import dataclass, field
 from typing import Optional
 
 import torch
@@ -21,6 +22,9 @@ from ..moe import ExpertParallelMoE
 from ..ops import LayerNorm
 from ..parallel.tensor import Attention
 from .gpt2 import GPT2Config, GPT2Embedding, GPT2Head
+
+
+EXPERT_IMPLS = ("loop", "batched", "grouped")
 
 
 @dataclass
@@ -36,6 +40,16 @@ class MoEConfig:
     aux_loss_weight: float = 0.01
     causal: bool = True
     tie_weights: bool = True
+    # expert FFN implementation: "loop" (per-expert padded segments),
+    # "batched" (BatchedExperts) or "grouped" (GroupedExperts, the grouped
+    # HIP GEMM).  Default from TDPA_MOE_EXPERTS (docs/knobs.md).
+    expert_impl: str = field(
+        default_factory=lambda: os.environ.get("TDPA_MOE_EXPERTS", "loop"))
+
+    def __post_init__(self):
+        if self.expert_impl not in EXPERT_IMPLS:
+            raise ValueError(f"expert_impl must be one of {EXPERT_IMPLS}, "
+                             f"got {self.expert_impl!r}")
 
 
 def mixtral_style_8x() -> MoEConfig:
@@ -50,12 +64,19 @@ class MoEBlock(nn.Module):
         self.ln_1 = LayerNorm(cfg.dim, **kw)
         self.attn = Attention(cfg.dim, cfg.n_head, causal=cfg.causal, **kw)
         self.ln_2 = LayerNorm(cfg.dim, **kw)
-        # batched=False: the per-expert segment path measured FASTER at
-        # the moe_8x bench scale (93.7k vs 80.9k tok/s — its narrow()
-        # slices are zero-copy; BatchedExperts' gathers cost more than the
-        # padding fills they remove, profiles/r02_notes.md)
+        # "loop" (default): the per-expert segment path measured FASTER
+        # than "batched" at the moe_8x bench scale (93.7k vs 80.9k tok/s —
+        # its narrow() slices are zero-copy; BatchedExperts' gathers cost
+        # more than the padding fills they remove, profiles/r02_notes.md).
+        # "grouped" runs the grouped HIP GEMM on the sorted buffer in place
+        # (no padding, no gather) and measured 113.6k vs 95.0k tok/s for
+        # "loop" at the same scale (docs/design/kernels.md "Grouped expert
+        # GEMM").  It stays opt-in for now.
         self.moe = ExpertParallelMoE(cfg.dim, cfg.num_experts, cfg.top_k,
-                                     cfg.hidden_mult, **kw)
+                                     cfg.hidden_mult,
+                                     batched=cfg.expert_impl == "batched",
+                                     grouped=cfg.expert_impl == "grouped",
+                                     **kw)
 
     def forward(self, x):
         x = x + self.attn(self.ln_1(x))

@@ -1,2 +1,2 @@
-from .layer import (ExpertParallelMoE, TopKRouter, Expert,
-                    mark_expert_parallel, is_expert_param)
+from .layer import (ExpertParallelMoE, TopKRouter, Expert, BatchedExperts,
+                    GroupedExperts, mark_expert_parallel, is_expert_param)

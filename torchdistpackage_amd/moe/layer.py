@@ -191,6 +191,24 @@ class BatchedExperts(nn.Module):
         return y.reshape(-1, D).index_select(0, val_idx)
 
 
+class GroupedExperts(BatchedExperts):
+    """All local experts as stacked (E, ...) parameters (the layout and
+    ``load_from_experts`` of BatchedExperts), run on the sorted token buffer
+    IN PLACE: two ``ops.grouped_linear`` calls walk the per-expert row
+    segments given by a device offset table.  No padding, no gather, no
+    per-expert launch; on eligible GPU shapes each GEMM is one HIP launch
+    for all experts and nothing reads the routing on the host."""
+
+    def forward(self, grouped: torch.Tensor,
+                offs: torch.Tensor) -> torch.Tensor:
+        """grouped (N, D) tokens sorted by local expert; offs (E+1,) row
+        offsets on grouped's device; returns (N, D) in the same order."""
+        from ..ops import grouped_linear
+        h = grouped_linear(grouped, self.w1, offs, self.b1)
+        h = bias_gelu(h)         # fc1 bias went into the GEMM epilogue
+        return grouped_linear(h, self.w2, offs, self.b2)
+
+
 def _all_to_all_uneven(x: torch.Tensor, in_splits: List[int],
                        out_splits: List[int],
                        group: Optional[dist.ProcessGroup]) -> torch.Tensor:
@@ -252,8 +270,12 @@ class ExpertParallelMoE(nn.Module):
                  hidden_mult: int = 4,
                  ep_group: Optional[dist.ProcessGroup] = None,
                  batched: bool = False,
+                 grouped: bool = False,
                  device=None, dtype=None):
         super().__init__()
+        if batched and grouped:
+            raise ValueError("ExpertParallelMoE: batched and grouped are "
+                             "exclusive")
         if ep_group is None:
             try:
                 from ..dist.topo import tpc
@@ -273,7 +295,12 @@ class ExpertParallelMoE(nn.Module):
         self.router = TopKRouter(dim, num_experts, top_k, device=device,
                                  dtype=dtype)
         self.batched = batched
-        if batched:
+        self.grouped = grouped
+        if grouped:
+            self.experts_g = GroupedExperts(self.num_local, dim, hidden_mult,
+                                            device=device, dtype=dtype)
+            mark_expert_parallel(self.experts_g)
+        elif batched:
             self.experts_b = BatchedExperts(self.num_local, dim, hidden_mult,
                                             device=device, dtype=dtype)
             mark_expert_parallel(self.experts_b)
@@ -352,7 +379,13 @@ class ExpertParallelMoE(nn.Module):
         # every UNSEEN (M,N,K) costs a host-side hipBLASLt heuristic pass
         # (~5-10 ms): unquantized expert GEMMs made deep MoE forwards
         # host-bound (measured 90 ms/block cold vs 2 ms warm).
-        if self.batched:
+        if self.grouped:
+            # segment table built on the device; nothing below reads it on
+            # the host
+            cnt_dev = my_slice.sum(0).to(received.device)
+            offs = F.pad(torch.cumsum(cnt_dev, 0), (1, 0))
+            y_all = self.experts_g(grouped, offs)
+        elif self.batched:
             cnt_dev = my_slice.sum(0).to(received.device)
             y_all = self.experts_b(grouped, cnt_dev,
                                    max(per_expert) if per_expert else 0)

@@ -845,3 +845,11 @@ def swiglu(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     """silu(a) * b, fused (backward recomputes sigmoid — nothing extra
     saved beyond a and b)."""
     return _SwiGluFn.apply(a, b)
+
+
+# ---------------------------------------------------------------------------
+# grouped linear over ragged expert segments (MoE expert FFN)
+# ---------------------------------------------------------------------------
+
+from .grouped import (GROUPED_GEMM_BM, grouped_gemm_eligible,  # noqa: E402
+                      grouped_linear)

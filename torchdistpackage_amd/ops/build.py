@@ -28,6 +28,7 @@ SOURCES = [
     "rope_swiglu.hip",
     "gemv.hip",
     "decode_attn.hip",
+    "grouped_gemm.hip",
 ]
 
 

@@ -1,6 +1,8 @@
 // Python bindings for the in-tree gfx950 HIP extension (_tdpa_hip).
 #include <torch/extension.h>
 
+#include "grouped_gemm_plan.h"
+
 std::vector<torch::Tensor> rmsnorm_fwd(torch::Tensor x, torch::Tensor w,
                                        double eps);
 std::vector<torch::Tensor> rmsnorm_bwd(torch::Tensor dy, torch::Tensor x,
@@ -80,6 +82,15 @@ torch::Tensor decode_attention(torch::Tensor q, torch::Tensor k_cache,
                                torch::Tensor v_cache, torch::Tensor out,
                                c10::optional<torch::Tensor> pos_t, long pos0,
                                double scale, long split_kv);
+torch::Tensor grouped_gemm_fprop(torch::Tensor x, torch::Tensor w,
+                                 torch::Tensor offs,
+                                 c10::optional<torch::Tensor> bias);
+torch::Tensor grouped_gemm_dgrad(torch::Tensor dy, torch::Tensor w,
+                                 torch::Tensor offs);
+std::tuple<torch::Tensor, c10::optional<torch::Tensor>> grouped_gemm_wgrad(
+    torch::Tensor dy, torch::Tensor x, torch::Tensor offs,
+    bool want_bias_grad);
+torch::Tensor grouped_gemm_plan(torch::Tensor offs_cpu, int64_t T);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rmsnorm_fwd", &rmsnorm_fwd);
@@ -121,4 +132,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemv_bf16", &gemv_bf16);
   m.def("rope_apply_pos", &rope_apply_pos);
   m.def("decode_attention", &decode_attention);
+  m.def("grouped_gemm_fprop", &grouped_gemm_fprop);
+  m.def("grouped_gemm_dgrad", &grouped_gemm_dgrad);
+  m.def("grouped_gemm_wgrad", &grouped_gemm_wgrad);
+  m.def("grouped_gemm_plan", &grouped_gemm_plan,
+        "(offs_cpu, T) -> (row-tile bound, 3) int64: (expert, first row, "
+        "row count) per block, expert -1 = idle");
+  m.attr("GROUPED_GEMM_BM") = GG_BM;
 }
