@@ -181,6 +181,170 @@ class LayerNorm(torch.nn.Module):
 
 
 # ---------------------------------------------------------------------------
+# fused residual-stream junctions (docs/design/kernels.md "Fused residual
+# kernels"): bias add + residual add + LayerNorm in one pass forward, and
+# LayerNorm backward + residual-grad add + bias-grad column sum in one pass
+# backward.  Results are those of the unfused ops bit for bit, except the
+# bias grads, whose fp32 summation order changes.
+# ---------------------------------------------------------------------------
+
+# TDPA_FUSED_RESIDUAL=0 restores the unfused composition (read once, here)
+_FUSED_RESIDUAL = os.environ.get("TDPA_FUSED_RESIDUAL", "1") != "0"
+
+
+def fused_residual_enabled() -> bool:
+    return _FUSED_RESIDUAL
+
+
+def set_fused_residual(on: bool) -> bool:
+    """Switch the fused residual kernels on or off for this process; returns
+    the previous setting.  For tests and same-process A/B runs."""
+    global _FUSED_RESIDUAL
+    prev, _FUSED_RESIDUAL = _FUSED_RESIDUAL, bool(on)
+    return prev
+
+
+def _bf16_rows_ok(*ts) -> bool:
+    """Same-shape, contiguous, 16-byte aligned bf16 device tensors whose
+    last dim is a multiple of 8: what the fused kernels read and write."""
+    t0 = ts[0]
+    if t0.dim() < 1 or t0.numel() == 0 or t0.shape[-1] % 8 != 0:
+        return False
+    return all(t.is_cuda and t.dtype == torch.bfloat16 and t.is_contiguous()
+               and t.shape == t0.shape and t.device == t0.device
+               and t.data_ptr() % 16 == 0 for t in ts)
+
+
+def _bf16_vecs_ok(like, *vs) -> bool:
+    D = like.shape[-1]
+    return all(v is None or (
+        v.is_cuda and v.dtype == torch.bfloat16 and v.is_contiguous()
+        and v.numel() == D and v.device == like.device
+        and v.data_ptr() % 16 == 0) for v in vs)
+
+
+def _fused_ln_ok(x, weight, bias, *more_rows, vec=None) -> bool:
+    return (_FUSED_RESIDUAL and _bf16_rows_ok(x, *more_rows)
+            and x.shape[-1] <= ext("layer_norm").fused_ln_max_d()
+            and _bf16_vecs_ok(x, weight, bias, vec))
+
+
+def _ln_bwd_residual(dh, x, weight, mean, rstd, g_res, want_colsum):
+    """(g, dw, db, dbias or None) from the fused backward kernel."""
+    g, partial = ext("layer_norm").layernorm_bwd_residual(
+        dh.contiguous(), x, weight, mean, rstd, g_res.contiguous(),
+        want_colsum)
+    # one sum(0) per slice, not one sum(1): torch's reduction then splits
+    # exactly as in layernorm_bwd, which keeps dw and db bit-identical to it
+    # (measured: sum(1) changes db at (16384, 2048))
+    sums = [partial[k].sum(0).to(weight.dtype)
+            for k in range(partial.shape[0])]
+    return g, sums[0], sums[1], (sums[2] if want_colsum else None)
+
+
+class _LayerNormForkFn(torch.autograd.Function):
+    """(x, h = layer_norm(x)) with x handed through, so that the grad of
+    everything else that reads x (the residual stream) arrives in this
+    backward and is added inside the LayerNorm backward kernel."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, eps):
+        h, mean, rstd = ext("layer_norm").layernorm_fwd(x, weight, bias, eps)
+        ctx.save_for_backward(x, weight, mean, rstd)
+        ctx.set_materialize_grads(False)    # a missing grad arrives as None
+        return x, h
+
+    @staticmethod
+    def backward(ctx, gx, gh):
+        x, weight, mean, rstd = ctx.saved_tensors
+        if gh is None:
+            return gx, None, None, None
+        if gx is None:
+            dx, dw, db = ext("layer_norm").layernorm_bwd(
+                gh.contiguous(), x, weight, mean, rstd)
+            return dx, dw, db, None
+        g, dw, db, _ = _ln_bwd_residual(gh, x, weight, mean, rstd, gx, False)
+        return g, dw, db, None
+
+
+def layer_norm_fork(x, weight, bias, eps: float = 1e-5):
+    """``(x, layer_norm(x))`` for a pre-LN residual block: use the returned
+    x for the residual path.  On the fused path the backward makes
+    ``grad(x) = layer-norm input grad + grad(returned x)`` in one kernel
+    instead of a LayerNorm backward and a separate add."""
+    if _fused_ln_ok(x, weight, bias) and x.shape[-1] == weight.numel():
+        return _LayerNormForkFn.apply(x, weight, bias, eps)
+    return x, layer_norm(x, weight, bias, eps)
+
+
+class _BiasResidualLayerNormFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, y, lin_bias, x_res, weight, bias, eps):
+        x_new, h, mean, rstd = ext("layer_norm").bias_residual_layernorm_fwd(
+            y, lin_bias, x_res, weight, bias, eps)
+        ctx.save_for_backward(x_new, weight, mean, rstd)
+        ctx.has_lin_bias = lin_bias is not None
+        ctx.set_materialize_grads(False)    # a missing grad arrives as None
+        return x_new, h
+
+    @staticmethod
+    def backward(ctx, gx, gh):
+        x_new, weight, mean, rstd = ctx.saved_tensors
+        # the column sum only where the linear's bias wants a grad
+        has_b = ctx.has_lin_bias and ctx.needs_input_grad[1]
+        D = x_new.shape[-1]
+        if gh is None:
+            if gx is None:
+                return None, None, None, None, None, None
+            dlb = gx.reshape(-1, D).sum(0) if has_b else None
+            return gx, dlb, gx, None, None, None
+        if gx is None:
+            g, dw, db = ext("layer_norm").layernorm_bwd(
+                gh.contiguous(), x_new, weight, mean, rstd)
+            dlb = g.reshape(-1, D).sum(0) if has_b else None
+            return g, dlb, g, dw, db, None
+        g, dw, db, dlb = _ln_bwd_residual(gh, x_new, weight, mean, rstd, gx,
+                                          has_b)
+        return g, dlb, g, dw, db, None
+
+
+def bias_residual_layer_norm(y, lin_bias, x_res, weight, bias,
+                             eps: float = 1e-5):
+    """``x_new = x_res + (y + lin_bias)`` and ``h = layer_norm(x_new)`` as
+    ``(x_new, h)``: the junction between a Row-parallel linear (its output y
+    without the bias, ``lin_bias`` may be None) and the next LayerNorm.  The
+    fused kernels make the roundings of the unfused ops, so x_new, h and all
+    grads but ``lin_bias``'s (fp32 summation order) are bit-identical."""
+    if _fused_ln_ok(x_res, weight, bias, y, vec=lin_bias) \
+            and x_res.shape[-1] == weight.numel():
+        return _BiasResidualLayerNormFn.apply(y, lin_bias, x_res, weight,
+                                              bias, eps)
+    x_new = x_res + (y if lin_bias is None else y + lin_bias)
+    return x_new, layer_norm(x_new, weight, bias, eps)
+
+
+class _BiasResidualAddFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, y, lin_bias, x_res):
+        ctx.has_lin_bias = lin_bias is not None
+        return ext("bias_residual_add").bias_residual_add(y, lin_bias, x_res)
+
+    @staticmethod
+    def backward(ctx, g):
+        dlb = g.reshape(-1, g.shape[-1]).sum(0) \
+            if ctx.has_lin_bias and ctx.needs_input_grad[1] else None
+        return g, dlb, g
+
+
+def bias_residual_add(y, lin_bias, x_res):
+    """``x_res + (y + lin_bias)`` in one pass (``lin_bias`` may be None)."""
+    if _FUSED_RESIDUAL and _bf16_rows_ok(x_res, y) \
+            and _bf16_vecs_ok(x_res, lin_bias):
+        return _BiasResidualAddFn.apply(y, lin_bias, x_res)
+    return x_res + (y if lin_bias is None else y + lin_bias)
+
+
+# ---------------------------------------------------------------------------
 # fused bias + GELU (tanh approximation, GPT-2 convention)
 # ---------------------------------------------------------------------------
 
@@ -212,6 +376,15 @@ class _BiasGeluFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, bias = ctx.saved_tensors
+        if x.is_cuda and ctx.has_bias:
+            dy, xc = dy.contiguous(), x.contiguous()
+            if _bf16_rows_ok(xc, dy) and _bf16_vecs_ok(xc, bias) and \
+                    ext("bias_gelu").bias_gelu_bwd_colsum_ok(x.shape[-1]):
+                # the kernel sums the columns of the dx it stores: no
+                # second pass over dx for the bias grad
+                dx, partial = ext("bias_gelu").bias_gelu_bwd_colsum(
+                    dy, xc, bias)
+                return dx, partial.sum(0).to(x.dtype)
         if x.is_cuda:
             dx = ext("bias_gelu").bias_gelu_bwd(dy.contiguous(),
                                                 x.contiguous(), bias)

@@ -240,36 +240,64 @@ __global__ void attn_fwd_kernel(const unsigned short* __restrict__ q,
 
 // ---------------------------------------------------------------- backward
 
+template <int LPR>
 __global__ void attn_delta_kernel(const unsigned short* __restrict__ o,
                                   const unsigned short* __restrict__ dout,
                                   float* __restrict__ delta,
                                   Strides os, Strides ds,
-                                  int B, int H, int S, int D) {
-  // one wave per row, GRID-STRIDED (a one-row-per-block launch was
-  // dispatch-bound: 65k tiny blocks cost 3x the memory floor)
+                                  int B, int H, int S) {
+  // LPR = D / 8 lanes per row, each with one 16-byte load of o and of dout,
+  // so every lane of the wave loads: 4 rows per wave at D = 128, 8 at
+  // D = 64.  (One wave per row left 48 resp. 56 of 64 lanes idle and ran at
+  // about 3x the memory floor.)  GRID-STRIDED over rows; the loop bound is
+  // wave-uniform so the shuffles below always see whole lane groups.  A lane
+  // sums its 8 products in order and the group adds by xor butterfly, which
+  // is the order the one-wave-per-row form had: its lanes past LPR held 0.
   const long rows = (long)B * H * S;
-  const int wpb = blockDim.x / WAVE;
   const int lane = threadIdx.x % WAVE;
-  const long stride = (long)gridDim.x * wpb;
-  for (long row = (long)blockIdx.x * wpb + threadIdx.x / WAVE; row < rows;
-       row += stride) {
-    int s = row % S;
-    int h = (row / S) % H;
-    int b = row / ((long)S * H);
-    const unsigned short* orow = o + b * os.b + h * os.h + (long)s * os.s;
-    const unsigned short* drow = dout + b * ds.b + h * ds.h + (long)s * ds.s;
+  const int sub = lane % LPR;
+  constexpr int RPW = WAVE / LPR;
+  const long wave = (long)blockIdx.x * (blockDim.x / WAVE) + threadIdx.x / WAVE;
+  const long stride = (long)gridDim.x * (blockDim.x / WAVE) * RPW;
+  for (long row0 = wave * RPW; row0 < rows; row0 += stride) {
+    const long row = row0 + lane / LPR;
     float acc = 0.f;
-    for (int i = lane * 8; i < D; i += WAVE * 8) {
-      bf16x8_v ov = pack8(orow + i);
-      bf16x8_v dv = pack8(drow + i);
+    if (row < rows) {
+      int s = row % S;
+      int h = (row / S) % H;
+      int b = row / ((long)S * H);
+      const unsigned short* orow = o + b * os.b + h * os.h + (long)s * os.s;
+      const unsigned short* drow = dout + b * ds.b + h * ds.h + (long)s * ds.s;
+      bf16x8_v ov = pack8(orow + sub * 8);
+      bf16x8_v dv = pack8(drow + sub * 8);
       const unsigned short* op = (const unsigned short*)&ov;
       const unsigned short* dp = (const unsigned short*)&dv;
 #pragma unroll
       for (int j = 0; j < 8; ++j) acc += bf2f(op[j]) * bf2f(dp[j]);
     }
-    acc = wave_sum(acc);
-    if (lane == 0) delta[row] = acc;
+#pragma unroll
+    for (int off = LPR / 2; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+    if (sub == 0 && row < rows) delta[row] = acc;
   }
+}
+
+// delta = rowsum(o * dout) as (B, H, S) fp32; o and dout checked by the caller
+void launch_attn_delta(const torch::Tensor& o, const torch::Tensor& dout,
+                       torch::Tensor& delta, Strides os, Strides dos, int B,
+                       int H, int S, int D, hipStream_t stream) {
+  const long rows = (long)B * H * S;
+  const int rpb = 4 * (WAVE / (D / 8));      // rows per 256-thread block
+  long blocks = (rows + rpb - 1) / rpb;
+  if (blocks > 2048) blocks = 2048;          // grid-stride the rest
+  const unsigned short* op = (const unsigned short*)o.data_ptr();
+  const unsigned short* dp = (const unsigned short*)dout.data_ptr();
+  float* delp = delta.data_ptr<float>();
+  if (D == 128)
+    hipLaunchKernelGGL(attn_delta_kernel<16>, dim3((unsigned)blocks),
+                       dim3(256), 0, stream, op, dp, delp, os, dos, B, H, S);
+  else
+    hipLaunchKernelGGL(attn_delta_kernel<8>, dim3((unsigned)blocks),
+                       dim3(256), 0, stream, op, dp, delp, os, dos, B, H, S);
 }
 
 template <int D, bool CAUSAL, int NW>
@@ -794,15 +822,7 @@ std::vector<torch::Tensor> attn_bwd(torch::Tensor dout, torch::Tensor q,
           os = get_strides(o), dos = get_strides(dout),
           dqs = get_strides(dq), dks = get_strides(dk), dvs = get_strides(dv);
 
-  {
-    long rows = (long)B * H * S;
-    long blocks = (rows + 3) / 4;
-    if (blocks > 2048) blocks = 2048;   // grid-stride the rest
-    hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)blocks), dim3(256),
-                       0, stream, (const unsigned short*)o.data_ptr(),
-                       (const unsigned short*)dout.data_ptr(),
-                       delta.data_ptr<float>(), os, dos, B, H, S, D);
-  }
+  launch_attn_delta(o, dout, delta, os, dos, B, H, S, D, stream);
 
   const AttnBwdRoute route = attn_bwd_select(attn_knobs_ref(), B, H, S, D);
   if (!route.v1) {
@@ -838,4 +858,24 @@ std::vector<torch::Tensor> attn_bwd(torch::Tensor dout, torch::Tensor q,
 #undef LAUNCH_BWD
   HIP_CHECK_LAST();
   return {dq, dk, dv};
+}
+
+// The backward's first pass on its own: delta = rowsum(o * dout), (B, H, S)
+// fp32, from (B, H, S, D) bf16 views with a contiguous last dim.
+torch::Tensor attn_delta(torch::Tensor o, torch::Tensor dout) {
+  TORCH_CHECK(o.is_cuda() && o.scalar_type() == torch::kBFloat16 &&
+                  o.dim() == 4,
+              "attn_delta: o must be a (B, H, S, D) bf16 device tensor");
+  const int64_t B = o.size(0), H = o.size(1), S = o.size(2), D = o.size(3);
+  TORCH_CHECK(D == 64 || D == 128,
+              "attn_delta: head_dim must be 64 or 128, got ", D);
+  TORCH_CHECK(B >= 1 && H >= 1 && S >= 1, "attn_delta: empty problem, o is ",
+              o.sizes());
+  check_operand("attn_delta", "o", o, o, B, H, S, D);
+  check_operand("attn_delta", "dout", dout, o, B, H, S, D);
+  auto delta = torch::empty({B, H, S}, o.options().dtype(torch::kFloat));
+  launch_attn_delta(o, dout, delta, get_strides(o), get_strides(dout), (int)B,
+                    (int)H, (int)S, (int)D, at::cuda::getCurrentHIPStream());
+  HIP_CHECK_LAST();
+  return delta;
 }

@@ -91,6 +91,21 @@ std::tuple<torch::Tensor, c10::optional<torch::Tensor>> grouped_gemm_wgrad(
     torch::Tensor dy, torch::Tensor x, torch::Tensor offs,
     bool want_bias_grad);
 torch::Tensor grouped_gemm_plan(torch::Tensor offs_cpu, int64_t T);
+std::vector<torch::Tensor> bias_residual_layernorm_fwd(
+    torch::Tensor y, c10::optional<torch::Tensor> bias, torch::Tensor x_res,
+    torch::Tensor ln_w, torch::Tensor ln_b, double eps);
+std::vector<torch::Tensor> layernorm_bwd_residual(
+    torch::Tensor dh, torch::Tensor x, torch::Tensor w, torch::Tensor mean,
+    torch::Tensor rstd, torch::Tensor g_res, bool want_colsum);
+std::vector<torch::Tensor> bias_gelu_bwd_colsum(torch::Tensor dy,
+                                                torch::Tensor x,
+                                                torch::Tensor bias);
+bool bias_gelu_bwd_colsum_ok(int64_t D);
+int64_t fused_ln_max_d();
+torch::Tensor bias_residual_add(torch::Tensor y,
+                                c10::optional<torch::Tensor> bias,
+                                torch::Tensor x_res);
+torch::Tensor attn_delta(torch::Tensor o, torch::Tensor dout);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rmsnorm_fwd", &rmsnorm_fwd);
@@ -139,4 +154,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "(offs_cpu, T) -> (row-tile bound, 3) int64: (expert, first row, "
         "row count) per block, expert -1 = idle");
   m.attr("GROUPED_GEMM_BM") = GG_BM;
+  m.def("bias_residual_layernorm_fwd", &bias_residual_layernorm_fwd,
+        "(y, bias|None, x_res, ln_w, ln_b, eps) -> (x_new, h, mean, rstd)");
+  m.def("layernorm_bwd_residual", &layernorm_bwd_residual,
+        "(dh, x, w, mean, rstd, g_res, want_colsum) -> (g, partial): "
+        "fp32 (2|3, grid, D); partial[k].sum(0), one sum per slice, = dw, db"
+        "[, colsum(g)] (one sum(1) would change the bits of dw and db)");
+  m.def("bias_gelu_bwd_colsum", &bias_gelu_bwd_colsum,
+        "(dy, x, bias) -> (dx, partial): partial.sum(0) = colsum(dx) in fp32");
+  m.def("fused_ln_max_d", &fused_ln_max_d,
+        "widest last dim of the fused LayerNorm kernels");
+  m.def("bias_gelu_bwd_colsum_ok", &bias_gelu_bwd_colsum_ok,
+        "whether bias_gelu_bwd_colsum covers last dim D");
+  m.def("bias_residual_add", &bias_residual_add,
+        "(y, bias|None, x_res) -> bf16(x_res + bf16(y + bias))");
+  m.def("attn_delta", &attn_delta,
+        "(o, dout) (B, H, S, D) bf16 -> rowsum(o * dout) (B, H, S) fp32");
 }

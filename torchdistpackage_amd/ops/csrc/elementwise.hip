@@ -12,6 +12,7 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 #include "common.h"
+#include "fused_checks.h"
 
 namespace {
 
@@ -39,6 +40,21 @@ DEVINL float gelu_df(float u) {
   float t = tanh_fast(GELU_C * (u + GELU_A * u * u2));
   return 0.5f * (1.f + t) +
          0.5f * u * (1.f - t * t) * GELU_C * (1.f + 3.f * GELU_A * u2);
+}
+
+// gelu_df for bias_gelu_bwd_bf16 (vector path and tail), with the contraction
+// written out: which multiply fuses with which add is otherwise the
+// compiler's choice per use (with the column sums added to the loop it fused
+// one element pair differently, and dx moved by a bf16 ulp on ~1e-4 of the
+// elements where the two terms cancel).  This is the sequence the plain
+// kernel has always compiled to, so its dx is unchanged.
+DEVINL float gelu_df_pinned(float u) {
+#pragma clang fp contract(off)
+  float u2 = u * u;
+  float t = tanh_fast(GELU_C * fmaf(GELU_A * u, u2, u));
+  float k = fmaf(u2, 3.f * GELU_A, 1.f);
+  float m = 0.5f * u * fmaf(-t, t, 1.f) * GELU_C * k;
+  return fmaf(1.f + t, 0.5f, m);
 }
 
 // -------- bias_gelu: x (rows, D) bf16, bias (D) bf16 (or empty) ----------
@@ -74,13 +90,30 @@ __global__ void bias_gelu_fwd_bf16(const unsigned short* __restrict__ x,
   }
 }
 
+// COLSUM == true also gives the column sums of the dx it stores (the fc1
+// bias grad), so nothing has to read dx back.  It is the same flat
+// grid-stride loop, launched with a grid whose stride gridDim.x * BLOCK * 8
+// is a multiple of D: then a thread stays on the same 8 columns in every
+// iteration, its rows are (i0 / D) + k * (stride / D), and it keeps 8 fp32
+// sums of the bf16-rounded dx it stored.  The sums go to partial[i0 ..
+// i0 + 8), which makes ``partial`` a (stride / D, D) matrix of per-row-lane
+// column sums; the caller finishes with a sum over dim 0.  The element
+// arithmetic is one piece of code for both forms, so dx does not depend on
+// which one ran.
+template <bool COLSUM>
 __global__ void bias_gelu_bwd_bf16(const unsigned short* __restrict__ dy,
                                    const unsigned short* __restrict__ x,
                                    const unsigned short* __restrict__ bias,
                                    unsigned short* __restrict__ dx,
+                                   float* __restrict__ partial,
                                    long n, int D, int has_bias) {
   long i0 = ((long)blockIdx.x * BLOCK + threadIdx.x) * 8;
   long stride = (long)gridDim.x * BLOCK * 8;
+  float acc[8];
+  if constexpr (COLSUM) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] = 0.f;
+  }
   for (long i = i0; i < n; i += stride) {
     if (i + 8 <= n) {
       bf16x8 xv = *(const bf16x8*)(x + i);
@@ -95,15 +128,22 @@ __global__ void bias_gelu_bwd_bf16(const unsigned short* __restrict__ dy,
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         float b = has_bias ? bf2f(bs[j]) : 0.f;
-        os[j] = f2bf(bf2f(gs[j]) * gelu_df(bf2f(xs[j]) + b));
+        os[j] = f2bf(bf2f(gs[j]) * gelu_df_pinned(bf2f(xs[j]) + b));
+        if constexpr (COLSUM) acc[j] += bf2f(os[j]);
       }
       *(bf16x8*)(dx + i) = out;
     } else {
+      // never with COLSUM: its caller requires D % 8 == 0, so n % 8 == 0
       for (long j = i; j < n; ++j) {
         float b = has_bias ? bf2f(bias[j % D]) : 0.f;
-        dx[j] = f2bf(bf2f(dy[j]) * gelu_df(bf2f(x[j]) + b));
+        dx[j] = f2bf(bf2f(dy[j]) * gelu_df_pinned(bf2f(x[j]) + b));
       }
     }
+  }
+  if constexpr (COLSUM) {
+    *(float4*)(partial + i0) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+    *(float4*)(partial + i0 + 4) =
+        make_float4(acc[4], acc[5], acc[6], acc[7]);
   }
 }
 
@@ -129,6 +169,36 @@ __global__ void bias_gelu_bwd_f32(const float* __restrict__ dy,
   for (long i = i0; i < n; i += stride) {
     float b = has_bias ? bias[i % D] : 0.f;
     dx[i] = dy[i] * gelu_df(x[i] + b);
+  }
+}
+
+// out = bf16(x + bf16(y + bias)): the Row-parallel bias add and the residual
+// add that follows it, in one pass with the two roundings of the two passes.
+// bias may be null (then out = bf16(x + y)).  D % 8 == 0.
+__global__ void bias_residual_add_bf16(const unsigned short* __restrict__ y,
+                                       const unsigned short* __restrict__ bias,
+                                       const unsigned short* __restrict__ x,
+                                       unsigned short* __restrict__ out,
+                                       long n, int D) {
+  long i0 = ((long)blockIdx.x * BLOCK + threadIdx.x) * 8;
+  long stride = (long)gridDim.x * BLOCK * 8;
+  for (long i = i0; i < n; i += stride) {   // n % 8 == 0
+    bf16x8 yv = *(const bf16x8*)(y + i);
+    bf16x8 xv = *(const bf16x8*)(x + i);
+    bf16x8 bv;
+    if (bias != nullptr) bv = *(const bf16x8*)(bias + (int)(i % D));
+    const unsigned short* ys = (const unsigned short*)&yv;
+    const unsigned short* xs = (const unsigned short*)&xv;
+    const unsigned short* bs = (const unsigned short*)&bv;
+    bf16x8 ov;
+    unsigned short* os = (unsigned short*)&ov;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      float t = bf2f(ys[j]);
+      if (bias != nullptr) t = bf2f(f2bf(t + bf2f(bs[j])));
+      os[j] = f2bf(bf2f(xs[j]) + t);
+    }
+    *(bf16x8*)(out + i) = ov;
   }
 }
 
@@ -355,11 +425,13 @@ torch::Tensor bias_gelu_bwd(torch::Tensor dy, torch::Tensor x,
   auto stream = at::cuda::getCurrentHIPStream();
   if (x.scalar_type() == torch::kBFloat16) {
     TORCH_CHECK(!has_bias || (D % 8 == 0), "D must be multiple of 8");
-    hipLaunchKernelGGL(bias_gelu_bwd_bf16, dim3(ew_grid(n, 8)), dim3(BLOCK), 0,
-                       stream, (const unsigned short*)dy.data_ptr(),
+    hipLaunchKernelGGL(bias_gelu_bwd_bf16<false>, dim3(ew_grid(n, 8)),
+                       dim3(BLOCK), 0, stream,
+                       (const unsigned short*)dy.data_ptr(),
                        (const unsigned short*)x.data_ptr(),
                        (const unsigned short*)bias.data_ptr(),
-                       (unsigned short*)dx.data_ptr(), n, D, has_bias);
+                       (unsigned short*)dx.data_ptr(), (float*)nullptr, n, D,
+                       has_bias);
   } else {
     hipLaunchKernelGGL(bias_gelu_bwd_f32, dim3(ew_grid(n)), dim3(BLOCK), 0,
                        stream, dy.data_ptr<float>(), x.data_ptr<float>(),
@@ -368,6 +440,91 @@ torch::Tensor bias_gelu_bwd(torch::Tensor dy, torch::Tensor x,
   }
   HIP_CHECK_LAST();
   return dx;
+}
+
+namespace {
+// grid of the COLSUM form of bias_gelu_bwd_bf16: a multiple of
+// q = D / gcd(D, BLOCK * 8) blocks, so that the grid's stride is a multiple
+// of D; as many as the flat kernel would get (at most 2048), at least q.
+// 0 if q itself is above 2048 blocks.
+long colsum_grid(long n, int D) {
+  long a = D, b = (long)BLOCK * 8;
+  while (b) { long t = a % b; a = b; b = t; }
+  const long q = D / a;
+  if (q > 2048) return 0;
+  const long want = ew_grid(n, 8);
+  return want < q ? q : want / q * q;
+}
+}  // namespace
+
+// (dx, partial): dx as bias_gelu_bwd, and fp32 (lanes, D) partial column sums
+// of dx; partial.sum(0) is the bias grad.  bf16 with a bias only, and D must
+// pass bias_gelu_bwd_colsum_ok.
+std::vector<torch::Tensor> bias_gelu_bwd_colsum(torch::Tensor dy,
+                                                torch::Tensor x,
+                                                torch::Tensor bias) {
+  const char* fn = "bias_gelu_bwd_colsum";
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == torch::kBFloat16 &&
+                  x.is_contiguous() && x.dim() >= 1 && aligned16(x),
+              fn, ": x must be a contiguous, 16-byte aligned bf16 device "
+              "tensor");
+  const int D = x.size(-1);
+  TORCH_CHECK(D > 0 && D % 8 == 0, fn, ": D must be a multiple of 8, got ", D);
+  check_bf16_rows(fn, "dy", dy, x);
+  check_bf16_vec(fn, "bias", bias, x, D);
+  const long rows = x.numel() / D;
+  auto dx = torch::empty_like(x);
+  auto opts = x.options().dtype(torch::kFloat);
+  if (rows == 0) return {dx, torch::zeros({1, (long)D}, opts)};
+  // (16384, 8192): 2048 blocks, a (512, 8192) partial of 16 MB against the
+  // 268 MB read of dx it replaces
+  const long grid = colsum_grid(x.numel(), D);
+  TORCH_CHECK(grid > 0, fn, ": no grid of at most 2048 blocks has a stride "
+              "that is a multiple of D = ", D);
+  auto partial = torch::empty({grid * BLOCK * 8 / D, (long)D}, opts);
+  auto stream = at::cuda::getCurrentHIPStream();
+  hipLaunchKernelGGL(bias_gelu_bwd_bf16<true>, dim3((unsigned)grid),
+                     dim3(BLOCK), 0, stream,
+                     (const unsigned short*)dy.data_ptr(),
+                     (const unsigned short*)x.data_ptr(),
+                     (const unsigned short*)bias.data_ptr(),
+                     (unsigned short*)dx.data_ptr(),
+                     partial.data_ptr<float>(), x.numel(), D, 1);
+  HIP_CHECK_LAST();
+  return {dx, partial};
+}
+
+bool bias_gelu_bwd_colsum_ok(int64_t D) {
+  return D > 0 && D % 8 == 0 && colsum_grid(1, (int)D) > 0;
+}
+
+// bf16(x_res + bf16(y + bias)) in one pass; bias may be absent.
+torch::Tensor bias_residual_add(torch::Tensor y,
+                                c10::optional<torch::Tensor> bias,
+                                torch::Tensor x_res) {
+  const char* fn = "bias_residual_add";
+  TORCH_CHECK(x_res.is_cuda() && x_res.scalar_type() == torch::kBFloat16 &&
+                  x_res.is_contiguous() && x_res.dim() >= 1 &&
+                  aligned16(x_res),
+              fn, ": x_res must be a contiguous, 16-byte aligned bf16 device "
+              "tensor");
+  const int D = x_res.size(-1);
+  TORCH_CHECK(D > 0 && D % 8 == 0, fn, ": D must be a multiple of 8, got ", D);
+  check_bf16_rows(fn, "y", y, x_res);
+  const bool has_bias = bias.has_value() && bias->defined();
+  if (has_bias) check_bf16_vec(fn, "bias", *bias, x_res, D);
+  auto out = torch::empty_like(x_res);
+  const long n = x_res.numel();
+  if (n == 0) return out;
+  auto stream = at::cuda::getCurrentHIPStream();
+  hipLaunchKernelGGL(bias_residual_add_bf16, dim3(ew_grid(n, 8)), dim3(BLOCK),
+                     0, stream, (const unsigned short*)y.data_ptr(),
+                     has_bias ? (const unsigned short*)bias->data_ptr()
+                              : (const unsigned short*)nullptr,
+                     (const unsigned short*)x_res.data_ptr(),
+                     (unsigned short*)out.data_ptr(), n, D);
+  HIP_CHECK_LAST();
+  return out;
 }
 
 void adamw_step(torch::Tensor p, torch::Tensor g, torch::Tensor m,

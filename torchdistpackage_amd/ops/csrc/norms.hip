@@ -13,6 +13,7 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 #include "common.h"
+#include "fused_checks.h"
 
 namespace {
 
@@ -346,11 +347,22 @@ __global__ void rmsnorm_bwd_bf16v8(const unsigned short* __restrict__ dy,
 // The row's chunks stay in registers (NC chunks of 8 per thread, as in the
 // *_reg backward kernels): x is read from memory once, and the second pass
 // of an off-centre row costs no memory traffic.
-template <int NC>
+//
+// RES == true is the fused junction: the row normalised is
+// x_new = bf16(x + bf16(lin + lbias)), formed in registers from the linear
+// output ``lin``, its bias (may be null) and the residual stream x, and
+// stored to ``xnew``.  The two bf16 roundings are those of the unfused
+// ``x + (lin + lbias)``, and everything after them is the RES == false code
+// on the same values in the same order, so x_new, y, mean and rstd are
+// bit-identical to layer_norm(x + (lin + lbias)).
+template <int NC, bool RES>
 __global__ void __launch_bounds__(BLOCK)
 layernorm_fwd_bf16v8(const unsigned short* __restrict__ x,
+                     const unsigned short* __restrict__ lin,
+                     const unsigned short* __restrict__ lbias,
                      const unsigned short* __restrict__ w,
                      const unsigned short* __restrict__ b,
+                     unsigned short* __restrict__ xnew,
                      unsigned short* __restrict__ y,
                      float* __restrict__ mean,
                      float* __restrict__ rstd,
@@ -367,6 +379,19 @@ layernorm_fwd_bf16v8(const unsigned short* __restrict__ x,
       int i = threadIdx.x * 8 + c * BLOCK * 8;
       if (i < D) {
         xv[c] = load8f(xr + i);
+        if constexpr (RES) {
+          f8 t = load8f(lin + (long)row * D + i);
+          if (lbias != nullptr) {
+            f8 lb = load8f(lbias + i);
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+              t.v[j] = bf2f(f2bf(t.v[j] + lb.v[j]));
+          }
+#pragma unroll
+          for (int j = 0; j < 8; ++j)
+            xv[c].v[j] = bf2f(f2bf(xv[c].v[j] + t.v[j]));
+          store8f(xnew + (long)row * D + i, xv[c]);
+        }
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           s += xv[c].v[j];
@@ -557,22 +582,40 @@ __global__ void rmsnorm_bwd_bf16_reg(const unsigned short* __restrict__ dy,
   }
 }
 
-template <int NC>
-__global__ void layernorm_bwd_bf16_reg(const unsigned short* __restrict__ dy,
-                                       const unsigned short* __restrict__ x,
-                                       const unsigned short* __restrict__ w,
-                                       const float* __restrict__ mean,
-                                       const float* __restrict__ rstd,
-                                       unsigned short* __restrict__ dx,
-                                       float* __restrict__ dw_partial,
-                                       float* __restrict__ db_partial,
-                                       int rows, int D) {
+// RES == true also adds the residual-stream grad: the row stored is
+// g = bf16(float(bf16(dx)) + g_res), which is what autograd's accumulation of
+// the LayerNorm input grad and the residual grad gives.  g_res is loaded in
+// the second per-row loop, so it is not held across the block reduction.
+// COLSUM == true (needs RES) keeps a third accumulator set: the column sums
+// of the stored g, i.e. the bias grad of the linear whose output entered the
+// junction.  dw and db accumulate exactly as without RES.
+template <int NC, bool RES, bool COLSUM>
+__global__ void __launch_bounds__(BLOCK)
+layernorm_bwd_bf16_reg(const unsigned short* __restrict__ dy,
+                       const unsigned short* __restrict__ x,
+                       const unsigned short* __restrict__ w,
+                       const float* __restrict__ mean,
+                       const float* __restrict__ rstd,
+                       const unsigned short* __restrict__ g_res,
+                       unsigned short* __restrict__ dx,
+                       float* __restrict__ dw_partial,
+                       float* __restrict__ db_partial,
+                       float* __restrict__ dc_partial,
+                       int rows, int D) {
+  static_assert(RES || !COLSUM, "COLSUM sums the residual-added grad");
   __shared__ float scratch[2 * BLOCK / WAVE];
   float acc_dw[NC][8], acc_db[NC][8];
+  float acc_dc[COLSUM ? NC : 1][8];
 #pragma unroll
   for (int c = 0; c < NC; ++c)
 #pragma unroll
     for (int j = 0; j < 8; ++j) { acc_dw[c][j] = 0.f; acc_db[c][j] = 0.f; }
+  if constexpr (COLSUM) {
+#pragma unroll
+    for (int c = 0; c < NC; ++c)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) acc_dc[c][j] = 0.f;
+  }
 
   for (int row = blockIdx.x; row < rows; row += gridDim.x) {
     const unsigned short* dyr = dy + (long)row * D;
@@ -626,6 +669,14 @@ __global__ void layernorm_bwd_bf16_reg(const unsigned short* __restrict__ dy,
           acc_dw[c][j] += dyv[c].v[j] * xhat;
           acc_db[c][j] += dyv[c].v[j];
         }
+        if constexpr (RES) {
+          f8 gr = load8f(g_res + (long)row * D + i);
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            out.v[j] = bf2f(f2bf(out.v[j])) + gr.v[j];
+            if constexpr (COLSUM) acc_dc[c][j] += bf2f(f2bf(out.v[j]));
+          }
+        }
         store8f(dxr + i, out);
       }
     }
@@ -642,6 +693,16 @@ __global__ void layernorm_bwd_bf16_reg(const unsigned short* __restrict__ dy,
         dwp[i + j] = acc_dw[c][j];
         dbp[i + j] = acc_db[c][j];
       }
+  }
+  if constexpr (COLSUM) {
+    float* dcp = dc_partial + (long)blockIdx.x * D;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      int i = threadIdx.x * 8 + c * BLOCK * 8;
+      if (i < D)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) dcp[i + j] = acc_dc[c][j];
+    }
   }
 }
 
@@ -761,10 +822,13 @@ std::vector<torch::Tensor> layernorm_fwd(torch::Tensor x, torch::Tensor w,
     // MAX_D = 8 chunks of BLOCK * 8
     const int nc = (D + BLOCK * 8 - 1) / (BLOCK * 8);
 #define LN_FWD(NC)                                                           \
-    hipLaunchKernelGGL(layernorm_fwd_bf16v8<NC>, grid, block, 0, stream,     \
-                       (const unsigned short*)x.data_ptr(),                  \
+    hipLaunchKernelGGL((layernorm_fwd_bf16v8<NC, false>), grid, block, 0,    \
+                       stream, (const unsigned short*)x.data_ptr(),          \
+                       (const unsigned short*)nullptr,                       \
+                       (const unsigned short*)nullptr,                       \
                        (const unsigned short*)w.data_ptr(),                  \
                        (const unsigned short*)b.data_ptr(),                  \
+                       (unsigned short*)nullptr,                             \
                        (unsigned short*)y.data_ptr(),                        \
                        mean.data_ptr<float>(), rstd.data_ptr<float>(),       \
                        (int)rows, D, (float)eps)
@@ -806,14 +870,17 @@ std::vector<torch::Tensor> layernorm_bwd(torch::Tensor dy, torch::Tensor x,
                                    x.options().dtype(torch::kFloat));
     int nc = (D + BLOCK * 8 - 1) / (BLOCK * 8);
 #define LN_REG(NC)                                                           \
-    hipLaunchKernelGGL(layernorm_bwd_bf16_reg<NC>, grid, block, 0, stream,   \
+    hipLaunchKernelGGL((layernorm_bwd_bf16_reg<NC, false, false>), grid,     \
+                       block, 0, stream,                                     \
                        (const unsigned short*)dy.data_ptr(),                 \
                        (const unsigned short*)x.data_ptr(),                  \
                        (const unsigned short*)w.data_ptr(),                  \
                        mean.data_ptr<float>(), rstd.data_ptr<float>(),       \
+                       (const unsigned short*)nullptr,                       \
                        (unsigned short*)dx.data_ptr(),                       \
                        dw_partial.data_ptr<float>(),                         \
-                       db_partial.data_ptr<float>(), (int)rows, D)
+                       db_partial.data_ptr<float>(), (float*)nullptr,        \
+                       (int)rows, D)
     if (nc == 1) LN_REG(1); else if (nc == 2) LN_REG(2);
     else if (nc == 3) LN_REG(3); else LN_REG(4);
 #undef LN_REG
@@ -861,4 +928,122 @@ std::vector<torch::Tensor> layernorm_bwd(torch::Tensor dy, torch::Tensor x,
   }
   HIP_CHECK_LAST();
   return {dx, dw.to(w.scalar_type()), db.to(w.scalar_type())};
+}
+
+// ------------------------------------------- fused residual-stream junction
+
+namespace {
+
+// the fused kernels cover what the register path covers: bf16, contiguous,
+// D % 8 == 0, D <= 4 chunks of BLOCK * 8
+constexpr int FUSED_LN_MAX_D = 4 * BLOCK * 8;
+
+int fused_ln_width(const char* fn, const torch::Tensor& x) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == torch::kBFloat16 &&
+                  x.is_contiguous() && x.dim() >= 1 && aligned16(x),
+              fn, ": needs a contiguous, 16-byte aligned bf16 device tensor");
+  const int D = x.size(-1);
+  TORCH_CHECK(D > 0 && D % 8 == 0 && D <= FUSED_LN_MAX_D, fn,
+              ": last dim must be a multiple of 8 up to ", FUSED_LN_MAX_D,
+              ", got ", D);
+  return D;
+}
+
+}  // namespace
+
+// widest last dim the fused LayerNorm kernels take (the Python gate asks)
+int64_t fused_ln_max_d() { return FUSED_LN_MAX_D; }
+
+// (x_new, h, mean, rstd) of h = layer_norm(x_new), x_new = x_res + (y + bias),
+// in one pass; bit-identical to the unfused ops.  bias may be absent.
+std::vector<torch::Tensor> bias_residual_layernorm_fwd(
+    torch::Tensor y, c10::optional<torch::Tensor> bias, torch::Tensor x_res,
+    torch::Tensor ln_w, torch::Tensor ln_b, double eps) {
+  const char* fn = "bias_residual_layernorm_fwd";
+  const int D = fused_ln_width(fn, x_res);
+  check_bf16_rows(fn, "y", y, x_res);
+  check_bf16_vec(fn, "ln_w", ln_w, x_res, D);
+  check_bf16_vec(fn, "ln_b", ln_b, x_res, D);
+  const bool has_bias = bias.has_value() && bias->defined();
+  if (has_bias) check_bf16_vec(fn, "bias", *bias, x_res, D);
+  const long rows = x_res.numel() / D;
+  auto x_new = torch::empty_like(x_res);
+  auto h = torch::empty_like(x_res);
+  auto mean = torch::empty({rows}, x_res.options().dtype(torch::kFloat));
+  auto rstd = torch::empty({rows}, x_res.options().dtype(torch::kFloat));
+  if (rows == 0) return {x_new, h, mean, rstd};
+  auto stream = at::cuda::getCurrentHIPStream();
+  dim3 grid(pick_grid(rows)), block(BLOCK);
+  const int nc = (D + BLOCK * 8 - 1) / (BLOCK * 8);
+#define LN_FWD_RES(NC)                                                       \
+  hipLaunchKernelGGL((layernorm_fwd_bf16v8<NC, true>), grid, block, 0,       \
+                     stream, (const unsigned short*)x_res.data_ptr(),        \
+                     (const unsigned short*)y.data_ptr(),                    \
+                     has_bias ? (const unsigned short*)bias->data_ptr()      \
+                              : (const unsigned short*)nullptr,              \
+                     (const unsigned short*)ln_w.data_ptr(),                 \
+                     (const unsigned short*)ln_b.data_ptr(),                 \
+                     (unsigned short*)x_new.data_ptr(),                      \
+                     (unsigned short*)h.data_ptr(),                          \
+                     mean.data_ptr<float>(), rstd.data_ptr<float>(),         \
+                     (int)rows, D, (float)eps)
+  // same chunk counts as layernorm_fwd, so the same reduction order
+  if (nc == 1) LN_FWD_RES(1); else if (nc == 2) LN_FWD_RES(2);
+  else LN_FWD_RES(4);
+#undef LN_FWD_RES
+  HIP_CHECK_LAST();
+  return {x_new, h, mean, rstd};
+}
+
+// (g, partial): g = layer-norm input grad + g_res, and partial, an fp32
+// (2 or 3, grid, D) tensor of per-block column sums: partial[0], [1] and,
+// with want_colsum, [2] summed over their dim 0 give dw, db and colsum(g).
+// The caller finishes with one sum(0) PER SLICE: a slice is reduced exactly
+// as layernorm_bwd's own partial is, which keeps dw and db bit-identical to
+// it; one sum(1) over the whole tensor does not.
+std::vector<torch::Tensor> layernorm_bwd_residual(
+    torch::Tensor dh, torch::Tensor x, torch::Tensor w, torch::Tensor mean,
+    torch::Tensor rstd, torch::Tensor g_res, bool want_colsum) {
+  const char* fn = "layernorm_bwd_residual";
+  const int D = fused_ln_width(fn, x);
+  check_bf16_rows(fn, "dh", dh, x);
+  check_bf16_rows(fn, "g_res", g_res, x);
+  check_bf16_vec(fn, "w", w, x, D);
+  const long rows = x.numel() / D;
+  TORCH_CHECK(mean.is_cuda() && rstd.is_cuda() &&
+                  mean.scalar_type() == torch::kFloat &&
+                  rstd.scalar_type() == torch::kFloat &&
+                  mean.is_contiguous() && rstd.is_contiguous() &&
+                  mean.numel() == rows && rstd.numel() == rows,
+              fn, ": mean and rstd must be contiguous fp32 with one value "
+              "per row (", rows, ")");
+  auto g = torch::empty_like(x);
+  dim3 grid(pick_grid(rows)), block(BLOCK);
+  const long np = want_colsum ? 3 : 2;
+  auto opts = x.options().dtype(torch::kFloat);
+  if (rows == 0) return {g, torch::zeros({np, 1, (long)D}, opts)};
+  auto partial = torch::empty({np, (long)grid.x, (long)D}, opts);
+  float* pp = partial.data_ptr<float>();
+  const long pstride = (long)grid.x * D;
+  auto stream = at::cuda::getCurrentHIPStream();
+  const int nc = (D + BLOCK * 8 - 1) / (BLOCK * 8);
+#define LN_REG_RES(NC, CS)                                                   \
+  hipLaunchKernelGGL((layernorm_bwd_bf16_reg<NC, true, CS>), grid, block, 0, \
+                     stream, (const unsigned short*)dh.data_ptr(),           \
+                     (const unsigned short*)x.data_ptr(),                    \
+                     (const unsigned short*)w.data_ptr(),                    \
+                     mean.data_ptr<float>(), rstd.data_ptr<float>(),         \
+                     (const unsigned short*)g_res.data_ptr(),                \
+                     (unsigned short*)g.data_ptr(), pp, pp + pstride,        \
+                     CS ? pp + 2 * pstride : (float*)nullptr, (int)rows, D)
+#define LN_REG_RES_NC(NC)                                                    \
+  do {                                                                       \
+    if (want_colsum) LN_REG_RES(NC, true); else LN_REG_RES(NC, false);       \
+  } while (0)
+  if (nc == 1) LN_REG_RES_NC(1); else if (nc == 2) LN_REG_RES_NC(2);
+  else if (nc == 3) LN_REG_RES_NC(3); else LN_REG_RES_NC(4);
+#undef LN_REG_RES_NC
+#undef LN_REG_RES
+  HIP_CHECK_LAST();
+  return {g, partial};
 }

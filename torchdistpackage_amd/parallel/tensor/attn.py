@@ -92,7 +92,9 @@ class TpAttention(nn.Module):
                                       sequence_parallel=sequence_parallel,
                                       device=device, dtype=dtype)
 
-    def forward(self, x):
+    def forward(self, x, skip_bias: bool = False):
+        """``skip_bias``: return the reduced out-projection WITHOUT
+        ``proj.bias``; the caller adds it."""
         if is_sequence_parallel(x):
             x = gather_from_sequence_parallel_region(x)
         else:
@@ -102,7 +104,7 @@ class TpAttention(nn.Module):
         # qkv layout per rank: [q_local | k_local | v_local] thanks to the
         # interleaved loader (init_qkv_weight_from_full) / native init
         o = _sdpa(qkv, self.n_head_local, self.causal)
-        return self.proj(o)
+        return self.proj(o, skip_bias=skip_bias)
 
     @torch.no_grad()
     def decode_step(self, x: torch.Tensor, k_cache: torch.Tensor,

@@ -56,7 +56,9 @@ class TpMlp(nn.Module):
                                      sequence_parallel=sequence_parallel,
                                      device=device, dtype=dtype)
 
-    def forward(self, x):
+    def forward(self, x, skip_bias: bool = False):
+        """``skip_bias``: return the reduced fc2 output WITHOUT ``fc2.bias``;
+        the caller adds it."""
         from .tp_utils import copy_to_tp_region, \
             gather_from_sequence_parallel_region
         if is_sequence_parallel(x):
@@ -70,7 +72,7 @@ class TpMlp(nn.Module):
         h = bias_gelu(h, self.fc1.bias)
         if self.dropout > 0 and self.training:
             h = F.dropout(h, p=self.dropout)
-        return self.fc2(h)
+        return self.fc2(h, skip_bias=skip_bias)
 
     @torch.no_grad()
     def init_weight_from_full(self, full_mlp: Mlp):

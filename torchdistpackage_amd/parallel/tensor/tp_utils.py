@@ -354,14 +354,16 @@ class RowParallelLinear(TpLinear):
         super().__init__(in_features // tp, out_features, bias=bias,
                          device=device, dtype=dtype)
 
-    def forward(self, x):
-        # bias added once, after the reduction (not per-rank!)
+    def forward(self, x, skip_bias: bool = False):
+        # bias added once, after the reduction (not per-rank!); with
+        # ``skip_bias`` the caller adds it (ParallelBlock folds it into the
+        # residual kernel that reads this output next)
         out = fast_linear(x, self.weight)
         if self.sequence_parallel and get_tp_size() > 1:
             out = reduce_scatter_to_sequence_parallel_region(out)
         else:
             out = reduce_from_tp_region(out)
-        if self.bias is not None:
+        if self.bias is not None and not skip_bias:
             out = out + self.bias
         return out
 

@@ -15,6 +15,7 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
+from ... import ops
 from ...ops import LayerNorm
 from .attn import Attention, TpAttention
 from .mlp import Mlp, TpMlp
@@ -73,6 +74,9 @@ class ParallelBlock(nn.Module):
             mark_sequence_parallel_params(self.ln_2)
 
     def forward(self, x):
+        if ops.fused_residual_enabled() and \
+                not (self.dropout > 0 and self.training):
+            return self._forward_fused(x)
         if self.sequence_parallel:
             x = maybe_split_into_sequence_parallel(x)
         h = self.ln_1(x)
@@ -87,6 +91,30 @@ class ParallelBlock(nn.Module):
         if self.sequence_parallel:
             set_sequence_parallel_attr(h)
         x = x + self.mlp(h)
+        if self.sequence_parallel:
+            set_sequence_parallel_attr(x)
+        return x
+
+    def _forward_fused(self, x):
+        """The same block with the residual-stream passes folded into their
+        neighbours (ops.layer_norm_fork, bias_residual_layer_norm,
+        bias_residual_add): the Row-parallel biases are added, after the
+        reduction as before, by the kernel that reads the linear's output
+        next.  Same values as ``forward``'s unfused code; shapes or dtypes
+        the kernels do not cover take the unfused ops inside each call."""
+        if self.sequence_parallel:
+            x = maybe_split_into_sequence_parallel(x)
+        ln_1, ln_2 = self.ln_1, self.ln_2
+        x, h = ops.layer_norm_fork(x, ln_1.weight, ln_1.bias, ln_1.eps)
+        if self.sequence_parallel:
+            set_sequence_parallel_attr(h)
+        a = self.attn(h, skip_bias=True)
+        x, h = ops.bias_residual_layer_norm(a, self.attn.proj.bias, x,
+                                            ln_2.weight, ln_2.bias, ln_2.eps)
+        if self.sequence_parallel:
+            set_sequence_parallel_attr(h)
+        m = self.mlp(h, skip_bias=True)
+        x = ops.bias_residual_add(m, self.mlp.fc2.bias, x)
         if self.sequence_parallel:
             set_sequence_parallel_attr(x)
         return x
