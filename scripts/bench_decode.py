@@ -2,7 +2,13 @@
 
 Prints prefill time and steady-state decode tokens/s (whole batch) —
 single GPU, bf16, random weights + synthetic prompt.
+
+``--int8`` runs the weight-only int8 A/B instead (scripts/_decode_ab.py):
+graphed decode, bf16 against ``quantize_linears_`` weights in the same
+process, B = 1 and 8 at max_seq/prompt 192/128 and 4096/2048 (the position
+table is built for 4096), ``--attn-impl`` in both arms.
 """
+import argparse
 import os
 import sys
 import time
@@ -23,6 +29,19 @@ B1 = os.environ.get("DEC_B1", "1") == "1"   # also run the batch-1 latency case
 dev = torch.device("cuda")
 torch.manual_seed(0)
 cfg = gpt2_xl_1p3b()
+ap = argparse.ArgumentParser()
+ap.add_argument("--int8", action="store_true")
+ap.add_argument("--attn-impl", default="hip", choices=("hip", "sdpa"))
+args = ap.parse_args()
+if args.int8:
+    from torchdistpackage_amd.inference.generate import GraphedGPT2Decoder
+    from _decode_ab import int8_ab
+    cfg.max_seq = 4096
+    m = GPT2Model(cfg, device=dev, dtype=torch.bfloat16).eval()
+    int8_ab(m, GraphedGPT2Decoder, cfg.vocab_size, args.attn_impl,
+            "gpt2-1.3b")
+    print("DECODE BENCH INT8 AB OK")
+    sys.exit(0)
 m = GPT2Model(cfg, device=dev, dtype=torch.bfloat16).eval()
 idx = torch.randint(0, cfg.vocab_size, (B, PROMPT), device=dev)
 hd = cfg.dim // cfg.n_head

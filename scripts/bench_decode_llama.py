@@ -1,4 +1,9 @@
-"""Llama-8B serving decode: graphed single-token step at B=1 and B=8."""
+"""Llama-8B serving decode: graphed single-token step at B=1 and B=8.
+
+``--int8`` runs the weight-only int8 A/B instead (scripts/_decode_ab.py):
+bf16 against ``quantize_linears_`` weights in the same process, B = 1 and 8
+at max_seq/prompt 192/128 and 4096/2048, ``--attn-impl`` in both arms."""
+import argparse
 import os
 import sys
 import time
@@ -13,7 +18,17 @@ from torchdistpackage_amd.models.llama import LlamaModel, llama3_8b
 PROMPT, NEW = 128, 64
 dev = torch.device("cuda")
 torch.manual_seed(0)
+ap = argparse.ArgumentParser()
+ap.add_argument("--int8", action="store_true")
+ap.add_argument("--attn-impl", default="hip", choices=("hip", "sdpa"))
+args = ap.parse_args()
 m = LlamaModel(llama3_8b(), device=dev, dtype=torch.bfloat16).eval()
+
+if args.int8:
+    from _decode_ab import int8_ab
+    int8_ab(m, GraphedLlamaDecoder, 128256, args.attn_impl, "llama-8b")
+    print("LLAMA DECODE INT8 AB OK")
+    sys.exit(0)
 
 for B in (1, 8):
     idx = torch.randint(0, 128256, (B, PROMPT), device=dev)

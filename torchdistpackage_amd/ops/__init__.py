@@ -1026,3 +1026,10 @@ def swiglu(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
 
 from .grouped import (GROUPED_GEMM_BM, grouped_gemm_eligible,  # noqa: E402
                       grouped_linear)
+
+# ---------------------------------------------------------------------------
+# weight-only int8 linear for decode (W8A16 GEMV kernel)
+# ---------------------------------------------------------------------------
+
+from .int8 import (Int8Weight, int8_linear, quantize_int8,  # noqa: E402
+                   quantize_linears_)

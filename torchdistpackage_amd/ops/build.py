@@ -27,6 +27,7 @@ SOURCES = [
     "gemm.hip",
     "rope_swiglu.hip",
     "gemv.hip",
+    "gemv_int8.hip",
     "decode_attn.hip",
     "grouped_gemm.hip",
 ]

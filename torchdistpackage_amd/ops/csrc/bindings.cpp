@@ -76,6 +76,9 @@ std::vector<torch::Tensor> ce_partial_fwd(torch::Tensor logits,
                                           torch::Tensor targets);
 torch::Tensor gemv_bf16(torch::Tensor x, torch::Tensor W,
                         c10::optional<torch::Tensor> bias);
+torch::Tensor gemv_w8a16(torch::Tensor x, torch::Tensor q,
+                         torch::Tensor scale,
+                         c10::optional<torch::Tensor> bias);
 torch::Tensor rope_apply_pos(torch::Tensor x, torch::Tensor cs,
                              torch::Tensor sn, torch::Tensor pos, bool fwd);
 torch::Tensor decode_attention(torch::Tensor q, torch::Tensor k_cache,
@@ -145,6 +148,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ce_bwd", &ce_bwd);
   m.def("ce_partial_fwd", &ce_partial_fwd);
   m.def("gemv_bf16", &gemv_bf16);
+  m.def("gemv_w8a16", &gemv_w8a16);
   m.def("rope_apply_pos", &rope_apply_pos);
   m.def("decode_attention", &decode_attention);
   m.def("grouped_gemm_fprop", &grouped_gemm_fprop);

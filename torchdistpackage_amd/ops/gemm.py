@@ -35,6 +35,7 @@ import torch
 import torch.nn.functional as F
 
 from . import ext
+from .int8 import Int8Weight, int8_linear
 
 _MODE = os.environ.get("TDPA_GEMM", "1")
 _GEMV = os.environ.get("TDPA_GEMV", "1") == "1"
@@ -74,6 +75,16 @@ def _use_gemv(M: int, N: int, K: int) -> bool:
     if M <= 4 and N <= 16384:
         return True
     return M <= 8 and K <= 4096 and N <= 16384
+
+
+def decode_route(M: int, N: int, K: int) -> str:
+    """What ``linear()`` runs under no_grad for a contiguous bf16 GPU weight
+    at these sizes with the current settings: ``"gemv"`` (csrc/gemv.hip) or
+    ``"hipBLASLt"``.  Mirrors the GEMV condition of ``linear()``; for
+    benchmark labels."""
+    if _MODE != "0" and _GEMV and K % 8 == 0 and _use_gemv(M, N, K):
+        return "gemv"
+    return "hipBLASLt"
 
 
 def _use_mine(kind: str, M: int, N: int, K: int) -> bool:
@@ -126,7 +137,10 @@ class _TdpaLinearFn(torch.autograd.Function):
 def linear(x: torch.Tensor, weight: torch.Tensor,
            bias: Optional[torch.Tensor] = None) -> torch.Tensor:
     """F.linear drop-in; routes 256-aligned bf16 GPU shapes through the
-    per-GEMM measured dispatch (in-tree MFMA kernel vs hipBLASLt)."""
+    per-GEMM measured dispatch (in-tree MFMA kernel vs hipBLASLt).  An
+    ``Int8Weight`` goes to ``int8_linear`` (ops/int8.py)."""
+    if isinstance(weight, Int8Weight):
+        return int8_linear(x, weight.q, weight.scale, bias)
     if (_MODE != "0" and x.is_cuda and x.dtype == torch.bfloat16
             and weight.dtype == torch.bfloat16
             and (bias is None or bias.dtype == torch.bfloat16)):

@@ -4,7 +4,8 @@ Reference parity: /root/reference/torchdistpackage/tools/module_replace.py:1-8
 plus the int8 swap-in pattern (bnb_fc.py / bminf_int8.py) generalized: the
 int8 libraries the reference wraps (bitsandbytes, bminf) are CUDA-only; the
 hooks here are optional-import guarded the same way the reference guards them
-(__init__.py:19-24).
+(__init__.py:19-24).  ``replace_linear_by_int8`` is the int8 swap-in that
+works on an MI355X: the in-tree W8A16 kernel (ops/int8.py).
 """
 
 from __future__ import annotations
@@ -52,3 +53,12 @@ def replace_linear_by_bminf(model: nn.Module) -> int:
         return bminf.QuantizedLinear(old)
 
     return replace_all_module(model, lambda m: isinstance(m, nn.Linear), factory)
+
+
+def replace_linear_by_int8(model: nn.Module, skip=()) -> int:
+    """Quantise the model's linears to weight-only int8 in place
+    (``ops.quantize_linears_``: per-output-channel scales, bf16 activations,
+    the W8A16 GEMV kernel on the decode path).  Returns the number of
+    converted modules."""
+    from ..ops import quantize_linears_
+    return quantize_linears_(model, skip=skip)
