@@ -18,7 +18,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
 from torchdistpackage_amd.inference.generate import (_alloc_caches,
-                                                     _gpt2_decode_forward)
+                                                     decode_forward)
 from torchdistpackage_amd.models.gpt2 import GPT2Model, gpt2_xl_1p3b
 
 B = int(os.environ.get("DEC_BATCH", "16"))
@@ -44,14 +44,12 @@ if args.int8:
     sys.exit(0)
 m = GPT2Model(cfg, device=dev, dtype=torch.bfloat16).eval()
 idx = torch.randint(0, cfg.vocab_size, (B, PROMPT), device=dev)
-hd = cfg.dim // cfg.n_head
-caches = _alloc_caches(cfg.n_layer, B, cfg.n_head, PROMPT + NEW, hd, dev,
-                       torch.bfloat16)
+caches = _alloc_caches(m, B, PROMPT + NEW)
 
 with torch.no_grad():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    logits = _gpt2_decode_forward(m, idx, caches, 0)
+    logits = decode_forward(m, idx, caches, 0)
     torch.cuda.synchronize()
     t_prefill = time.perf_counter() - t0
 
@@ -59,14 +57,14 @@ with torch.no_grad():
     pos0 = PROMPT
     # warmup decode steps
     for _ in range(8):
-        logits = _gpt2_decode_forward(m, nxt, caches, pos0)
+        logits = decode_forward(m, nxt, caches, pos0)
         nxt = logits.argmax(-1)[:, None]
         pos0 += 1
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     n_timed = NEW - 8
     for _ in range(n_timed):
-        logits = _gpt2_decode_forward(m, nxt, caches, pos0)
+        logits = decode_forward(m, nxt, caches, pos0)
         nxt = logits.argmax(-1)[:, None]
         pos0 += 1
     torch.cuda.synchronize()

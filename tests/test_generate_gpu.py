@@ -6,7 +6,7 @@ import torch
 
 from torchdistpackage_amd.inference import generate
 from torchdistpackage_amd.inference.generate import (_alloc_caches,
-                                                     _gpt2_decode_forward)
+                                                     decode_forward)
 from torchdistpackage_amd.models.gpt2 import GPT2Config, GPT2Model
 
 pytestmark = pytest.mark.gpu
@@ -21,13 +21,11 @@ def test_decode_logits_match_training_path():
     toks = torch.randint(0, cfg.vocab_size, (B, T), device="cuda")
     with torch.no_grad():
         full = m(toks)["logits"].float()        # (B, T, V)
-    hd = cfg.dim // cfg.n_head
-    caches = _alloc_caches(cfg.n_layer, B, cfg.n_head, T, hd,
-                           torch.device("cuda"), torch.bfloat16)
+    caches = _alloc_caches(m, B, T)
     # prefill 8 tokens, then single-token steps, teacher-forced
     pos0, chunk = 0, toks[:, :8]
     while chunk.shape[1] > 0:
-        logits = _gpt2_decode_forward(m, chunk, caches, pos0).float()
+        logits = decode_forward(m, chunk, caches, pos0).float()
         pos = pos0 + chunk.shape[1] - 1
         diff = (logits - full[:, pos]).abs().max().item()
         assert diff < 0.25, (pos, diff)   # bf16, two attention orders

@@ -11,8 +11,7 @@ import torch.nn as nn
 
 import torchdistpackage_amd.ops as ops
 from torchdistpackage_amd.inference.generate import (_alloc_caches,
-                                                     _gpt2_decode_forward,
-                                                     _llama_decode_forward)
+                                                     decode_forward)
 from torchdistpackage_amd.models.gpt2 import GPT2Config, GPT2Model
 from torchdistpackage_amd.models.llama import LlamaModel, llama_tiny
 from torchdistpackage_amd.ops.gemm import linear
@@ -144,16 +143,11 @@ def _oracle_twin(model):
 
 
 def _decode_logits(model, idx):
-    cfg = model.cfg
-    llama = hasattr(model.embed, "tok")
-    fwd = _llama_decode_forward if llama else _gpt2_decode_forward
-    n_kv = cfg.n_kv_head if llama else cfg.n_head
     B, T = idx.shape
-    caches = _alloc_caches(cfg.n_layer, B, n_kv, T, cfg.dim // cfg.n_head,
-                           idx.device, torch.float32)
-    out = [fwd(model, idx[:, :4], caches, 0)]       # prefill, then steps
+    caches = _alloc_caches(model, B, T)
+    out = [decode_forward(model, idx[:, :4], caches, 0)]    # prefill, steps
     for p in range(4, T):
-        out.append(fwd(model, idx[:, p:p + 1], caches, p))
+        out.append(decode_forward(model, idx[:, p:p + 1], caches, p))
     return torch.stack(out, 1)
 
 

@@ -341,18 +341,14 @@ def _models(family):
 
 
 def _decode_logits(model, toks):
-    from torchdistpackage_amd.inference.generate import (
-        _alloc_caches, _gpt2_decode_forward, _llama_decode_forward)
-    cfg = model.cfg
-    llama = hasattr(model.embed, "tok")
-    fwd = _llama_decode_forward if llama else _gpt2_decode_forward
+    from torchdistpackage_amd.inference.generate import (_alloc_caches,
+                                                         decode_forward)
     B, T = toks.shape
-    caches = _alloc_caches(cfg.n_layer, B,
-                           cfg.n_kv_head if llama else cfg.n_head, T,
-                           cfg.dim // cfg.n_head, toks.device, BF16)
-    out = [fwd(model, toks[:, :8], caches, 0).float()]
+    caches = _alloc_caches(model, B, T)
+    out = [decode_forward(model, toks[:, :8], caches, 0).float()]
     for p in range(8, T):
-        out.append(fwd(model, toks[:, p:p + 1], caches, p).float())
+        out.append(decode_forward(model, toks[:, p:p + 1], caches,
+                                  p).float())
     return out
 
 

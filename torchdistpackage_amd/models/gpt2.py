@@ -209,6 +209,30 @@ class GPT2Model(nn.Module):
                                              labels.transpose(0, 1))
         return out
 
+    @torch.no_grad()
+    def decode_forward(self, idx: torch.Tensor, caches, pos0,
+                       all_logits: bool = False,
+                       attn_impl: Optional[str] = None,
+                       mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """KV-cache forward (tp=1; see inference/generate.py) of ``idx``
+        (B, S_new) at absolute position ``pos0`` through ``caches``, one
+        (k, v) pair per block.  Returns the last position's logits (B, V),
+        or every position's (B, S_new, V) with ``all_logits`` (speculative
+        verification needs the whole chunk).  ``pos0`` is a host int, or
+        for the graphed single-token step a 1-element device tensor, with
+        ``mask`` on the SDPA route (parallel/tensor/attn.py
+        ``_cached_attention``)."""
+        S = idx.shape[1]
+        pos = pos0 if torch.is_tensor(pos0) else \
+            torch.arange(pos0, pos0 + S, device=idx.device)
+        x = self.embed.wte(idx) + self.embed.wpe(pos)[None, :, :]
+        x = x.transpose(0, 1).contiguous()          # (S, B, D)
+        for blk, (kc, vc) in zip(self.blocks, caches):
+            x = blk.decode_step(x, kc, vc, pos0, attn_impl, mask)
+        if all_logits:
+            return self.head(x)                     # (B, S, V)
+        return self.head(x[-1:])[:, -1]             # ln_f + tied head, (B, V)
+
     # -- pipeline partitioning support ----------------------------------
 
     def to_stage_layers(self) -> List[nn.Module]:

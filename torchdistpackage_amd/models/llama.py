@@ -21,6 +21,7 @@ import torch.nn as nn
 
 from ..ops import RMSNorm, flash_attention, rope_rotate_half, swiglu
 from ..ops.gemm import linear as fast_linear
+from ..parallel.tensor.attn import _cached_attention
 from ..parallel.tensor.tp_utils import (ColParallelLinear, RowParallelLinear,
                                         copy_to_tp_region,
                                         gather_from_sequence_parallel_region,
@@ -130,16 +131,18 @@ class LlamaAttention(nn.Module):
 
     @torch.no_grad()
     def decode_step(self, x: torch.Tensor, k_cache: torch.Tensor,
-                    v_cache: torch.Tensor, pos0: int,
-                    attn_impl: Optional[str] = None) -> torch.Tensor:
+                    v_cache: torch.Tensor, pos0,
+                    attn_impl: Optional[str] = None,
+                    mask: Optional[torch.Tensor] = None) -> torch.Tensor:
         """KV-cache inference step (tp=1 only; see inference/generate.py).
         RoPE is applied at the absolute positions ``pos0..pos0+S_new``; the
         cache holds rotated K, so cached entries are reused verbatim.
+        ``pos0`` is a host int, or a 1-element device tensor with ``mask``
+        for the graphed step: RoPE then reads its position on the device
+        (the host-scalar variant would bake one position into the graph).
         ``attn_impl="sdpa"`` expands K/V heads to Q heads for eager SDPA;
         ``"hip"`` runs the split-KV decode kernel on the un-expanded caches
         (ops.decode_attention); ``None`` reads ``TDPA_DECODE_ATTN``."""
-        from ..ops import decode_attention, resolve_decode_attn_impl
-        from ..parallel.tensor.attn import _cached_sdpa
         S, B, _ = x.shape
         q = fast_linear(x, self.wq.weight)
         k = fast_linear(x, self.wk.weight)
@@ -151,19 +154,8 @@ class LlamaAttention(nn.Module):
         q = self.rope(view4(q, self.nh_local), pos0)
         k = self.rope(view4(k, self.nkv_local), pos0)
         v = view4(v, self.nkv_local)
-        k_cache[:, :, pos0:pos0 + S] = k
-        v_cache[:, :, pos0:pos0 + S] = v
-        if resolve_decode_attn_impl(attn_impl) == "hip":
-            assert self.causal or S == 1, \
-                "decode_attention is causal over the new rows"
-            o = decode_attention(q, k_cache, v_cache, pos0)
-        else:
-            rep = self.nh_local // self.nkv_local
-            o = _cached_sdpa(q, k_cache.repeat_interleave(rep, dim=1),
-                             v_cache.repeat_interleave(rep, dim=1), pos0,
-                             self.causal)
-        o = o.permute(2, 0, 1, 3).reshape(S, B, self.nh_local * self.hd)
-        return self.wo(o)
+        return self.wo(_cached_attention(q, k, v, k_cache, v_cache, pos0,
+                                         self.causal, attn_impl, mask))
 
 
 class LlamaMlp(nn.Module):
@@ -217,9 +209,10 @@ class LlamaBlock(nn.Module):
         return x
 
     @torch.no_grad()
-    def decode_step(self, x, k_cache, v_cache, pos0: int, attn_impl=None):
+    def decode_step(self, x, k_cache, v_cache, pos0, attn_impl=None,
+                    mask=None):
         x = x + self.attn.decode_step(self.attn_norm(x), k_cache, v_cache,
-                                      pos0, attn_impl)
+                                      pos0, attn_impl, mask)
         return x + self.mlp(self.mlp_norm(x))
 
 
@@ -321,6 +314,20 @@ class LlamaModel(nn.Module):
             out["loss"] = cross_entropy_loss(logits.transpose(0, 1),
                                              labels.transpose(0, 1))
         return out
+
+    @torch.no_grad()
+    def decode_forward(self, idx: torch.Tensor, caches, pos0,
+                       all_logits: bool = False,
+                       attn_impl: Optional[str] = None,
+                       mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """KV-cache forward of ``idx`` (B, S_new) at ``pos0``; arguments
+        and result as GPT2Model.decode_forward."""
+        x = self.embed.tok(idx).transpose(0, 1).contiguous()
+        for blk, (kc, vc) in zip(self.blocks, caches):
+            x = blk.decode_step(x, kc, vc, pos0, attn_impl, mask)
+        if all_logits:
+            return self.head(x)
+        return self.head(x[-1:])[:, -1]
 
     def to_stage_layers(self) -> List[nn.Module]:
         return [self.embed, *self.blocks, self.head]

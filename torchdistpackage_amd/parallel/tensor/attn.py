@@ -18,8 +18,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ...ops import (decode_attention, fused_qkv_attention,
-                    resolve_decode_attn_impl)
+from ... import ops
+from ...ops import fused_qkv_attention, resolve_decode_attn_impl
 from .tp_utils import (ColParallelLinear, RowParallelLinear, TpLinear,
                        copy_to_tp_region, gather_from_sequence_parallel_region,
                        get_tp_size, is_sequence_parallel)
@@ -42,6 +42,60 @@ def _cached_sdpa(q: torch.Tensor, k_cache: torch.Tensor,
     mask = torch.arange(pos0 + S, device=q.device)[None, :] <= \
         (pos0 + torch.arange(S, device=q.device))[:, None]
     return F.scaled_dot_product_attention(q, ka, va, attn_mask=mask)
+
+
+def _cached_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
+                      k_cache: torch.Tensor, v_cache: torch.Tensor, pos0,
+                      causal: bool, attn_impl: Optional[str] = None,
+                      mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The one KV-cache attention step behind every ``decode_step``.
+
+    q (B, H, S, hd) and k, v (B, Hkv, S, hd), RoPE already applied; writes
+    k/v into the caches (B, Hkv, max_seq, hd) at ``pos0`` and returns the
+    attention output as (S, B, H*hd).  ``pos0`` has two forms, and each
+    keeps its own cache write and SDPA call (other kernels, other bf16
+    summation order — do not merge them):
+
+    * host int (eager decode, any S): slice-assign write, then
+      :func:`_cached_sdpa` over the valid prefix of the cache;
+    * 1-element int64 tensor (hipGraph-captured decode, S == 1): never read
+      back to the host; ``index_copy_`` write, then SDPA over the
+      full-length cache under the additive ``mask`` (1, 1, 1, max_seq) the
+      caller keeps open up to the current position.
+
+    ``attn_impl="hip"`` runs ops.decode_attention on the un-expanded caches
+    with either form; the SDPA routes expand K/V heads to Q heads first.
+    """
+    B, H, S, hd = q.shape
+    hip = resolve_decode_attn_impl(attn_impl) == "hip"
+    on_device = torch.is_tensor(pos0)
+    if on_device:
+        if S != 1:
+            raise ValueError(f"tensor pos0 is the single-token step, got "
+                             f"S={S}")
+        if not hip and mask is None:
+            raise ValueError("tensor pos0 with attn_impl='sdpa' needs the "
+                             "cache visibility mask")
+        k_cache.index_copy_(2, pos0, k)
+        v_cache.index_copy_(2, pos0, v)
+    else:
+        k_cache[:, :, pos0:pos0 + S] = k
+        v_cache[:, :, pos0:pos0 + S] = v
+    if hip:
+        assert causal or S == 1, \
+            "decode_attention is causal over the new rows"
+        o = ops.decode_attention(q, k_cache, v_cache, pos0)
+    else:
+        rep = H // k_cache.shape[1]
+        if rep != 1:
+            k_cache = k_cache.repeat_interleave(rep, dim=1)
+            v_cache = v_cache.repeat_interleave(rep, dim=1)
+        if on_device:
+            o = F.scaled_dot_product_attention(q, k_cache, v_cache,
+                                               attn_mask=mask)
+        else:
+            o = _cached_sdpa(q, k_cache, v_cache, pos0, causal)
+    return o.permute(2, 0, 1, 3).reshape(S, B, H * hd)
 
 
 def _sdpa(x_qkv: torch.Tensor, n_head: int, causal: bool) -> torch.Tensor:
@@ -108,16 +162,19 @@ class TpAttention(nn.Module):
 
     @torch.no_grad()
     def decode_step(self, x: torch.Tensor, k_cache: torch.Tensor,
-                    v_cache: torch.Tensor, pos0: int,
-                    attn_impl: Optional[str] = None) -> torch.Tensor:
+                    v_cache: torch.Tensor, pos0,
+                    attn_impl: Optional[str] = None,
+                    mask: Optional[torch.Tensor] = None) -> torch.Tensor:
         """KV-cache inference step (tp=1 only; see inference/generate.py).
 
         x (S_new, B, D) — the new tokens' hidden states; writes their K/V
         into ``k_cache``/``v_cache`` (B, H, max_seq, hd) at ``pos0`` and
-        attends q against positions [0, pos0+S_new).  ``attn_impl``:
-        ``"sdpa"`` = eager SDPA over the cache, ``"hip"`` = the split-KV
-        decode kernel (ops.decode_attention); ``None`` reads
-        ``TDPA_DECODE_ATTN`` (default sdpa).
+        attends q against positions [0, pos0+S_new).  ``pos0`` is a host
+        int, or a 1-element device tensor with ``mask`` for the graphed
+        step (see :func:`_cached_attention`).  ``attn_impl``: ``"sdpa"`` =
+        eager SDPA over the cache, ``"hip"`` = the split-KV decode kernel
+        (ops.decode_attention); ``None`` reads ``TDPA_DECODE_ATTN``
+        (default sdpa).
         """
         from ...ops.gemm import linear as fast_linear
         S, B, D = x.shape
@@ -129,17 +186,9 @@ class TpAttention(nn.Module):
         def v4(t):
             return t.reshape(S, B, hl, hd).permute(1, 2, 0, 3)
 
-        q, k, v = v4(q), v4(k), v4(v)
-        k_cache[:, :, pos0:pos0 + S] = k
-        v_cache[:, :, pos0:pos0 + S] = v
-        if resolve_decode_attn_impl(attn_impl) == "hip":
-            assert self.causal or S == 1, \
-                "decode_attention is causal over the new rows"
-            o = decode_attention(q, k_cache, v_cache, pos0)
-        else:
-            o = _cached_sdpa(q, k_cache, v_cache, pos0, self.causal)
-        o = o.permute(2, 0, 1, 3).reshape(S, B, hl * hd)
-        return self.proj(o)
+        return self.proj(_cached_attention(v4(q), v4(k), v4(v), k_cache,
+                                           v_cache, pos0, self.causal,
+                                           attn_impl, mask))
 
     @torch.no_grad()
     def init_from_full(self, full_attn: Attention):

@@ -120,12 +120,13 @@ class ParallelBlock(nn.Module):
         return x
 
     @torch.no_grad()
-    def decode_step(self, x, k_cache, v_cache, pos0: int, attn_impl=None):
+    def decode_step(self, x, k_cache, v_cache, pos0, attn_impl=None,
+                    mask=None):
         """KV-cache inference step (tp=1 only; see inference/generate.py):
         the training forward's SP plumbing is inert at tp=1, so LN/MLP are
         reused as-is and only attention takes the cache."""
         x = x + self.attn.decode_step(self.ln_1(x), k_cache, v_cache, pos0,
-                                      attn_impl)
+                                      attn_impl, mask)
         return x + self.mlp(self.ln_2(x))
 
     @torch.no_grad()
