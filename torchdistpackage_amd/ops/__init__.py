@@ -489,12 +489,17 @@ class _FlashAttentionFn(torch.autograd.Function):
 
 
 _ATTN_KNOBS = ("dq_recompute", "no_tr16", "pstore", "force_v1",
-               "max_ds_bytes")
+               "max_ds_bytes", "split_dkdv")
 
 
-def attention_knobs() -> dict:
-    """The run-time switches of the attention dispatch (docs/knobs.md)."""
-    return dict(zip(_ATTN_KNOBS, ext("attention_knobs").attn_knobs()))
+def attention_knobs(extended: bool = False) -> dict:
+    """The run-time switches of the attention dispatch (docs/knobs.md).  The
+    plain call keeps its five original keys (callers and tests compare the
+    key set); ``extended=True`` adds the later ones (``split_dkdv``)."""
+    cur = dict(zip(_ATTN_KNOBS, ext("attention_knobs").attn_knobs()))
+    if not extended:
+        cur = {n: cur[n] for n in _ATTN_KNOBS[:5]}
+    return cur
 
 
 @contextlib.contextmanager
@@ -508,7 +513,7 @@ def attention_route(**knobs):
         raise TypeError(f"unknown attention knob(s) {sorted(unknown)}; "
                         f"known: {_ATTN_KNOBS}")
     e = ext("attention_knobs")
-    cur = attention_knobs()
+    cur = attention_knobs(extended=True)
     cur.update(knobs)
     prev = e.attn_set_knobs(*(cur[n] for n in _ATTN_KNOBS))
     try:

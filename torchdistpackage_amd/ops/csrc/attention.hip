@@ -706,37 +706,41 @@ AttnKnobs& attn_knobs_ref() {
       std::getenv("TDPA_NO_TR16") != nullptr,
       std::getenv("TDPA_PSTORE") != nullptr,
       std::getenv("TDPA_ATTN_V1") != nullptr,
-      (int64_t)4 << 30};
+      (int64_t)4 << 30,
+      std::getenv("TDPA_SPLIT_DKDV") != nullptr};
   return k;
 }
 
-using KnobTuple = std::tuple<bool, bool, bool, bool, int64_t>;
+using KnobTuple = std::tuple<bool, bool, bool, bool, int64_t, bool>;
 
-// (dq_recompute, no_tr16, pstore, force_v1, max_ds_bytes)
+// (dq_recompute, no_tr16, pstore, force_v1, max_ds_bytes, split_dkdv)
 KnobTuple attn_knobs() {
   const AttnKnobs& k = attn_knobs_ref();
-  return {k.dq_recompute, k.no_tr16, k.pstore, k.force_v1, k.max_ds_bytes};
+  return {k.dq_recompute, k.no_tr16, k.pstore, k.force_v1, k.max_ds_bytes,
+          k.split_dkdv};
 }
 
 // Replaces the knobs; returns the previous ones.
 KnobTuple attn_set_knobs(bool dq_recompute, bool no_tr16, bool pstore,
-                         bool force_v1, int64_t max_ds_bytes) {
+                         bool force_v1, int64_t max_ds_bytes,
+                         bool split_dkdv) {
   KnobTuple prev = attn_knobs();
-  attn_knobs_ref() =
-      AttnKnobs{dq_recompute, no_tr16, pstore, force_v1, max_ds_bytes};
+  attn_knobs_ref() = AttnKnobs{dq_recompute, no_tr16,      pstore,
+                               force_v1,     max_ds_bytes, split_dkdv};
   return prev;
 }
 
 // Name of what attn_bwd_select gives a (B, H, S, D) problem under the
 // current knobs, the struct attn_bwd dispatches on: "v1", "v2_recompute", or
-// "v2_workspace" with "+pstore" / "+no_tr16" appended.
+// "v2_workspace" with "+pstore" / "+no_tr16" appended; "+split_dkdv" on
+// either v2 route where that knob alone selects the two-pass dk/dv kernels.
 std::string attn_bwd_route(int64_t B, int64_t H, int64_t S, int64_t D) {
   const AttnBwdRoute r = attn_bwd_select(attn_knobs_ref(), B, H, S, D);
   if (r.v1) return "v1";
-  if (r.recompute) return "v2_recompute";
-  std::string name = "v2_workspace";
+  std::string name = r.recompute ? "v2_recompute" : "v2_workspace";
   if (r.pstore) name += "+pstore";
   if (r.no_tr16) name += "+no_tr16";
+  if (r.split_dkdv) name += "+split_dkdv";
   return name;
 }
 
@@ -749,7 +753,8 @@ void attn_bwd_dq_v2(torch::Tensor dout, torch::Tensor q, torch::Tensor k,
 void attn_bwd_v2_all(torch::Tensor dout, torch::Tensor q, torch::Tensor k,
                      torch::Tensor v, torch::Tensor lse, torch::Tensor delta,
                      torch::Tensor dq, torch::Tensor dk, torch::Tensor dv,
-                     bool causal, double scale, const AttnBwdRoute& route);
+                     bool causal, double scale, const AttnBwdRoute& route,
+                     bool skip_dq = false);
 void attn_bwd_dkdv_v2(torch::Tensor dout, torch::Tensor q, torch::Tensor k,
                       torch::Tensor v, torch::Tensor lse, torch::Tensor delta,
                       torch::Tensor dk, torch::Tensor dv, bool causal,
@@ -858,6 +863,31 @@ std::vector<torch::Tensor> attn_bwd(torch::Tensor dout, torch::Tensor q,
 #undef LAUNCH_BWD
   HIP_CHECK_LAST();
   return {dq, dk, dv};
+}
+
+// The dk/dv stage of the head-dim-128 backward on its own, under the current
+// knobs: the fused kernel, or the two passes (scripts/kbench_attn_bwd.py
+// times one against the other).  delta from attn_delta; dk, dv as attn_bwd.
+void attn_bwd_dkdv(torch::Tensor dout, torch::Tensor q, torch::Tensor k,
+                   torch::Tensor v, torch::Tensor lse, torch::Tensor delta,
+                   torch::Tensor dk, torch::Tensor dv, bool causal,
+                   double scale) {
+  auto [B, H, Hkv, S, D] = check_qkv("attn_bwd_dkdv", q, k, v);
+  (void)Hkv;
+  check_operand("attn_bwd_dkdv", "dout", dout, q, B, H, S, D);
+  check_operand("attn_bwd_dkdv", "dk", dk, q, B, H, S, D);
+  check_operand("attn_bwd_dkdv", "dv", dv, q, B, H, S, D);
+  for (const torch::Tensor* t : {&lse, &delta})
+    TORCH_CHECK(t->is_cuda() && t->device() == q.device() &&
+                    t->scalar_type() == torch::kFloat && t->dim() == 3 &&
+                    t->size(0) == B && t->size(1) == H && t->size(2) == S &&
+                    t->is_contiguous(),
+                "attn_bwd_dkdv: lse and delta must be contiguous fp32 (", B,
+                ", ", H, ", ", S, ") tensors on q's device");
+  const AttnBwdRoute route = attn_bwd_select(attn_knobs_ref(), B, H, S, D);
+  TORCH_CHECK(!route.v1, "attn_bwd_dkdv: head dim 128 on the v2 route only");
+  attn_bwd_v2_all(dout, q, k, v, lse, delta, torch::Tensor(), dk, dv, causal,
+                  scale, route, /*skip_dq=*/true);
 }
 
 // The backward's first pass on its own: delta = rowsum(o * dout), (B, H, S)

@@ -562,10 +562,12 @@ void attn_bwd_dq_v2(torch::Tensor dout, torch::Tensor q, torch::Tensor k,
 }
 
 // ===========================================================================
-// dkdv v2: two passes (dv, then dk), each with the wave owning 32 KEYS
-// (lane = one key-column).  A single fused kernel needs both 64-register
-// accumulators plus K^T AND V^T fragments and spills ~240 B/lane; splitting
-// re-runs the QK^T MFMAs (cheap) but keeps both kernels spill-free.
+// dkdv v2, two-pass form (split_dkdv, pstore, no_tr16; the default is the
+// fused kernel further down): dv, then dk, each with the wave owning 32 KEYS
+// (lane = one key-column).  Fusing THIS layout needs both 64-register
+// accumulators plus K^T AND V^T fragments in registers and spills ~190
+// B/lane; the fused kernel fits by reading K rows from an LDS image and the
+// transposed operands by ds_read_b64_tr_b16 off the natural tiles.
 //   dv pass: S = mfma(Q, K^T regs); P = exp(S*scale - lse[q]);
 //            dv^T += mfma(dO^T, P-frag)
 //   dk pass: S as above + dP = mfma(dO, V^T regs);
@@ -887,6 +889,343 @@ void attn_bwd_dkdv_v2(torch::Tensor dout, torch::Tensor q, torch::Tensor k,
 }
 
 // ===========================================================================
+// Fused dk/dv (default): one sweep over the query tiles per 256-key block
+// produces dk, dv and, with WRITE_DS, the dS workspace.  The arithmetic is
+// the two passes' (same MFMAs, operands, masks, flush, fragment exchange and
+// accumulation order), so every output bit matches them; what goes is the
+// second staging of Q/dO, the second S chain and exp, and the transposed
+// tiles with their 16 two-byte LDS scatters per thread:
+//   - the block's 256 K rows sit in a 64 KB LDS image (written once) and are
+//     read as B-fragments by ds_read_b128 under swzK, which frees the 32
+//     registers kt_frag held; V^T fragments stay in registers
+//   - Q and dO tiles are staged once, double-buffered, into ONE image each
+//     (plain 256-byte rows, 16-byte chunks XORed with swzT's row key) that
+//     serves the row reads of S / dP and the transposed reads of dO^T / Q^T
+//   - dO^T and Q^T A-fragments come from ds_read_b64_tr_b16 (the builtin, so
+//     the compiler tracks lgkmcnt).  Gather model as verified by probe.hip:
+//     lane 4q+p of a 16-lane group supplies the address of row r0+q, columns
+//     c0+4p..c0+4p+3, and lane i receives column c0+i of those four rows.
+//     For the A-fragment A[d = ds*32 + l31][k = hi*8 + 4*sub + j] the block
+//     is rows r0 = qt*32 + kc*16 + hi*8 + sub*4, columns
+//     c0 = ds*32 + 16*((lane>>4)&1); under swzT the row key
+//     ((row&3)<<2 | (row>>2)&3) = (q<<2 | hi<<1 | sub) splits into a per-lane
+//     part and a compile-time part that is XORed in (tr_addr below).
+// Transposed reads need EXEC all ones: none sits in a divergent branch, and
+// the only early exit is the block-uniform kbase >= S.
+// ===========================================================================
+
+namespace {
+
+typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4_v;
+typedef __attribute__((address_space(3))) bf16x4_v lds_bf16x4;
+typedef __attribute__((address_space(3))) bf16x8_v lds_bf16x8;
+
+// Q/dO image, BYTE offset of 16-byte chunk ch (0..15) of row `row`
+DEVINL int swzT(int row, int ch) {
+  return row * (D2 * 2) + ((ch ^ (((row & 3) << 2) | ((row >> 2) & 3))) << 4);
+}
+
+template <bool CAUSAL, bool WRITE_DS>
+__launch_bounds__(512)
+__global__ void attn_bwd_dkdv_fused_v2_kernel(
+    const unsigned short* __restrict__ q,
+    const unsigned short* __restrict__ k,
+    const unsigned short* __restrict__ v,
+    const unsigned short* __restrict__ dout,
+    const float* __restrict__ lse,
+    const float* __restrict__ delta,
+    unsigned short* __restrict__ dk,
+    unsigned short* __restrict__ dv,
+    unsigned short* __restrict__ ds_out, long spad,
+    Strides2 qs, Strides2 ks, Strides2 vs, Strides2 dos, Strides2 dks,
+    Strides2 dvs, int B, int H, int S, float scale, int q_per_kv) {
+  // One 256-byte-aligned block: the XORs of the read addresses (bits 4-7)
+  // can then be applied to whole LDS addresses, and the dO tile sits at a
+  // constant 32 KB from the Q tile of the same buffer, so one address
+  // register plus `offset:` immediates serves both.
+  struct Images {
+    unsigned short q[2][KV * D2];    // 2 x 16 KB
+    unsigned short dO[2][KV * D2];   // 2 x 16 KB
+    unsigned short k[QT2 * D2];      // 64 KB
+  };
+  __shared__ __attribute__((aligned(256))) Images img;
+  constexpr unsigned kTile = KV * D2 * 2;          // bytes per Q or dO tile
+  constexpr unsigned kDoOff = 2 * kTile;           // Q tile -> dO tile
+  __shared__ float lse_lds[2][KV];
+  __shared__ float del_lds[2][KV];
+
+  const int bh = blockIdx.y;
+  const int bb = bh / H, hh = bh % H;
+  const int hkv = hh / q_per_kv;
+  const int kbase = blockIdx.x * QT2;
+  if (kbase >= S) return;
+  const int tid = threadIdx.x;
+  const int wid = tid / WAVE;
+  const int lane = tid % WAVE;
+  const int l31 = lane & 31;
+  const int hi = lane >> 5;
+
+  const unsigned short* qp = q + bb * qs.b + hh * qs.h;
+  const unsigned short* kp = k + bb * ks.b + hkv * ks.h;
+  const unsigned short* vp = v + bb * vs.b + hkv * vs.h;
+  const unsigned short* dop = dout + bb * dos.b + hh * dos.h;
+  const float* lsep = lse + (long)bh * S;
+  const float* delp = delta + (long)bh * S;
+
+  // this wave's 32 keys: V^T fragments in registers, K rows from k_img
+  const int key = kbase + wid * QW + l31;
+  bf16x8_v vt_frag[8];
+  {
+    long r = (long)(key < S ? key : S - 1);
+#pragma unroll
+    for (int c = 0; c < 8; ++c)
+      vt_frag[c] = pack8v(vp + r * vs.s + c * 16 + hi * 8);
+  }
+  // K image of the block's 256 keys, source rows clamped to S-1
+#pragma unroll
+  for (int c = 0; c < 8; ++c) {
+    int idx = tid * 8 + c * 4096;
+    int row = idx / D2;
+    int col = idx % D2;
+    int grow = kbase + row;
+    long r = (long)(grow < S ? grow : S - 1);
+    *(bf16x8_v*)((char*)img.k + swzT(row, col >> 3)) =
+        pack8v(kp + r * ks.s + col);
+  }
+  // row reads (Q, dO A-fragments; K B-fragments): row = 32*n + l31, chunk
+  // 2c + hi.  swzT's key only sees row & 15, so one per-lane offset serves
+  // all three images: off(c) = row_lane ^ (c << 5), plus the rows' 8 KB
+  const unsigned img_base = (unsigned)(unsigned long long)
+      (__attribute__((address_space(3))) unsigned short*)&img.q[0][0];
+  const unsigned row_lane = img_base + (unsigned)swzT(l31, hi);
+  const unsigned krow_lane = row_lane + 2 * kDoOff + wid * (QW * D2 * 2);
+
+  // per-lane part of the transposed-read byte address (within one tile)
+  const int tq = (lane >> 2) & 3;           // row within the 4-row block
+  const int tp = lane & 3;                  // 4-column group within 16
+  const int tg1 = (lane >> 4) & 1;          // which 16 of the 32 d columns
+  const unsigned tr_lane = img_base +
+      (unsigned)((hi * 8 + tq) * (D2 * 2) +
+                 (((tq << 2) | ((tg1 ^ hi) << 1) | (tp >> 1)) << 4) +
+                 (tp & 1) * 8);
+  // address of the Q-tile read for (qt, kc, sub, ds), tl = tr_lane plus the
+  // buffer's offset: the compile-time part of the chunk key is XORed in
+  // (bits 4 and 6-7, below the block's alignment), the rows are an immediate
+  auto tr_addr = [&](unsigned tl, int qt, int kc, int sub,
+                     int ds) -> unsigned {
+    return (tl ^ (unsigned)((((ds << 2) | sub)) << 4)) +
+           (unsigned)((qt * 32 + kc * 16 + sub * 4) * (D2 * 2));
+  };
+
+  f32x16 acc_dk[4], acc_dv[4];   // dk^T, dv^T (col = key)
+#pragma unroll
+  for (int ds = 0; ds < 4; ++ds) {
+    acc_dk[ds] = (f32x16)(0.f);
+    acc_dv[ds] = (f32x16)(0.f);
+  }
+
+  const int qt_start = CAUSAL ? kbase : 0;
+
+  auto stage = [&](int qt0, int b) {
+    // addresses are rebuilt from tid per tile, not held across the loop
+    int st = tid;
+    asm volatile("" : "+v"(st));
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      int idx = st * 8 + c * 4096;
+      int row = idx / D2;
+      int col = idx % D2;
+      int grow = qt0 + row;
+      long gr = (long)(grow < S ? grow : S - 1);
+      bf16x8_v qv = pack8v(qp + gr * qs.s + col);
+      bf16x8_v dv8 = pack8v(dop + gr * dos.s + col);
+      if (grow >= S) {
+        qv = (bf16x8_v)(__bf16)0.f;
+        dv8 = (bf16x8_v)(__bf16)0.f;
+      }
+      const int off = swzT(row, col >> 3);
+      *(bf16x8_v*)((char*)&img.q[b][0] + off) = qv;
+      *(bf16x8_v*)((char*)&img.dO[b][0] + off) = dv8;
+    }
+    if (tid < KV) {
+      int grow = qt0 + tid;
+      int gr = grow < S ? grow : S - 1;
+      float l = lsep[gr], d = delp[gr];
+      lse_lds[b][tid] = grow < S ? l : 0.f;
+      del_lds[b][tid] = grow < S ? d : 0.f;
+    }
+  };
+  stage(qt_start, 0);
+  __syncthreads();
+
+  // B-fragments over the q dimension (exchange as in the forward)
+  auto make_frag = [&](const f32x16& x, int kc, bf16x8_v& fb) {
+    int m0 = 2 * kc, m1 = 2 * kc + 1;
+    unsigned a0 = cvt_pk_bf16(x[4 * m0], x[4 * m0 + 1]);
+    unsigned a1 = cvt_pk_bf16(x[4 * m0 + 2], x[4 * m0 + 3]);
+    unsigned b0 = cvt_pk_bf16(x[4 * m1], x[4 * m1 + 1]);
+    unsigned b1 = cvt_pk_bf16(x[4 * m1 + 2], x[4 * m1 + 3]);
+    auto s0 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
+    auto s1 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
+    unsigned* dst = (unsigned*)&fb;
+    if (hi == 0) {
+      dst[0] = a0; dst[1] = a1; dst[2] = s0[1]; dst[3] = s1[1];
+    } else {
+      dst[0] = s0[0]; dst[1] = s1[0]; dst[2] = b0; dst[3] = b1;
+    }
+  };
+  auto tr_frag = [&](unsigned tl, unsigned img_off, int qt, int kc, int ds) {
+    bf16x4_v lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
+        (lds_bf16x4*)(tr_addr(tl, qt, kc, 0, ds) + img_off));
+    bf16x4_v hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
+        (lds_bf16x4*)(tr_addr(tl, qt, kc, 1, ds) + img_off));
+    return __builtin_shufflevector(lo, hi4, 0, 1, 2, 3, 4, 5, 6, 7);
+  };
+  auto row_frag = [&](unsigned addr) {
+    return *(const lds_bf16x8*)addr;
+  };
+
+  int buf = 0;
+  for (int qt0 = qt_start; qt0 < S; qt0 += KV) {
+    // keep the XORed address variants out of loop-invariant registers
+    // (one v_xor per read is free beside the MFMAs, 16 live registers are
+    // not): the loop sees the per-lane parts as fresh values
+    unsigned rl = row_lane + (unsigned)buf * kTile;
+    unsigned tl = tr_lane + (unsigned)buf * kTile;
+    unsigned kl = krow_lane;
+    asm volatile("" : "+v"(rl), "+v"(tl), "+v"(kl));
+
+#pragma unroll
+    for (int qt = 0; qt < 2; ++qt) {
+      __builtin_amdgcn_sched_barrier(0);
+      f32x16 s_acc = (f32x16)(0.f);
+      f32x16 dp_acc = (f32x16)(0.f);
+#pragma unroll
+      for (int c = 0; c < 8; ++c) {
+        const unsigned ra = (rl ^ (unsigned)(c << 5)) +
+                            (unsigned)(qt * 32 * D2 * 2);
+        bf16x8_v a_q = row_frag(ra);
+        bf16x8_v b_k = row_frag(kl ^ (unsigned)(c << 5));
+        s_acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+            a_q, b_k, s_acc, 0, 0, 0);
+        bf16x8_v a_do = row_frag(ra + kDoOff);
+        dp_acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+            a_do, vt_frag[c], dp_acc, 0, 0, 0);
+      }
+
+      // The chain is where registers peak (both accumulator sets, V^T, S,
+      // dP, operands in flight).  Left alone the scheduler front-loads all
+      // 24 operand reads; pin it to a two-step prefetch: the reads of
+      // steps c+1, c+2 are in flight while step c's two MFMAs issue
+      // (0x100 = DS read, 0x008 = MFMA).
+      __builtin_amdgcn_sched_group_barrier(0x100, 6, 0);
+#pragma unroll
+      for (int c = 0; c < 6; ++c) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+        __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
+      }
+      __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
+      // and the 32 lse/delta reads stay behind the chain
+      __builtin_amdgcn_sched_barrier(0);
+
+      // dS into s_acc, the dv operand (flushed P) into dp_acc; one half
+      // (the 16 query rows of k-chunk kc) at a time, so that only 8 lse and
+      // 8 delta values are live beside the accumulators
+      bf16x8_v fp[2], fds[2];
+#pragma unroll
+      for (int kc = 0; kc < 2; ++kc) {
+#pragma unroll
+        for (int r = 8 * kc; r < 8 * kc + 8; ++r) {
+          int qrel = qt * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+          int qrow = qt0 + qrel;
+          const bool valid = key < S && qrow < S && (!CAUSAL || key <= qrow);
+          const float e = __expf(s_acc[r] * scale - lse_lds[buf][qrel]);
+          const float p = valid ? e : 0.f;
+          // the dv MFMA gets an exact 0 for a negligible P (attn_knobs.h),
+          // folded into the mask's select; dS keeps the full P
+          const float pf = (valid && !(e < kAttnPFlush)) ? e : 0.f;
+          s_acc[r] = p * (dp_acc[r] - del_lds[buf][qrel]) * scale;
+          dp_acc[r] = pf;
+          if (WRITE_DS && qrow < S)
+            ds_out[((long)bh * S + qrow) * spad + key] = f2bf(s_acc[r]);
+        }
+        make_frag(dp_acc, kc, fp[kc]);
+        make_frag(s_acc, kc, fds[kc]);
+        // the next half, then the transposed reads, stay behind this one
+        __builtin_amdgcn_sched_barrier(0);
+      }
+
+      // dv^T += dO^T @ P   and   dk^T += Q^T @ dS
+#pragma unroll
+      for (int ds = 0; ds < 4; ++ds) {
+#pragma unroll
+        for (int kc = 0; kc < 2; ++kc) {
+          acc_dv[ds] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+              tr_frag(tl, kDoOff, qt, kc, ds), fp[kc], acc_dv[ds], 0, 0, 0);
+          acc_dk[ds] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+              tr_frag(tl, 0, qt, kc, ds), fds[kc], acc_dk[ds], 0, 0, 0);
+        }
+      }
+    }
+
+    if (qt0 + KV < S) stage(qt0 + KV, buf ^ 1);
+    __syncthreads();
+    buf ^= 1;
+  }
+
+  if (key < S) {
+    unsigned short* okp = dk + bb * dks.b + hh * dks.h + (long)key * dks.s;
+    unsigned short* ovp = dv + bb * dvs.b + hh * dvs.h + (long)key * dvs.s;
+#pragma unroll
+    for (int ds = 0; ds < 4; ++ds) {
+#pragma unroll
+      for (int blk = 0; blk < 4; ++blk) {
+        int d0 = ds * 32 + 8 * blk + 4 * hi;
+        unsigned short k4[4], v4[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          k4[j] = f2bf(acc_dk[ds][4 * blk + j]);
+          v4[j] = f2bf(acc_dv[ds][4 * blk + j]);
+        }
+        *(ushort4*)(okp + d0) = *(ushort4*)k4;
+        *(ushort4*)(ovp + d0) = *(ushort4*)v4;
+      }
+    }
+  }
+}
+
+// ds_ws null: no dS store (the recompute route)
+void launch_dkdv_fused(torch::Tensor& dout, torch::Tensor& q, torch::Tensor& k,
+                       torch::Tensor& v, torch::Tensor& lse,
+                       torch::Tensor& delta, torch::Tensor& dk,
+                       torch::Tensor& dv, unsigned short* ds_ws, long spad,
+                       bool causal, double scale) {
+  const int B = q.size(0), H = q.size(1), S = q.size(2);
+  const int q_per_kv = H / (int)k.size(1);
+  auto get = [](const torch::Tensor& t) {
+    return Strides2{t.stride(0), t.stride(1), t.stride(2)};
+  };
+  auto stream = at::cuda::getCurrentHIPStream();
+  dim3 grid((S + QT2 - 1) / QT2, B * H), block(512);
+#define L_FUSED(CC, WDS)                                                      \
+  hipLaunchKernelGGL((attn_bwd_dkdv_fused_v2_kernel<CC, WDS>), grid, block,   \
+                     0, stream, (const unsigned short*)q.data_ptr(),          \
+                     (const unsigned short*)k.data_ptr(),                     \
+                     (const unsigned short*)v.data_ptr(),                     \
+                     (const unsigned short*)dout.data_ptr(),                  \
+                     lse.data_ptr<float>(), delta.data_ptr<float>(),          \
+                     (unsigned short*)dk.data_ptr(),                          \
+                     (unsigned short*)dv.data_ptr(), ds_ws, spad, get(q),     \
+                     get(k), get(v), get(dout), get(dk), get(dv), B, H, S,    \
+                     (float)scale, q_per_kv)
+  if (ds_ws) { if (causal) L_FUSED(true, true); else L_FUSED(false, true); }
+  else { if (causal) L_FUSED(true, false); else L_FUSED(false, false); }
+#undef L_FUSED
+}
+
+}  // namespace
+
+// ===========================================================================
 // dq-lite: consumes the dS tile the dk pass stored instead of recomputing
 // S, P and dP per key-tile (48 -> 16 MFMAs per tile; no V/dO staging, no
 // exp, no lse/delta).  dS fragments load straight from global: the
@@ -1156,29 +1495,38 @@ __global__ void attn_bwd_dq_lite_tr_kernel(
 // Head dim 64, or force_v1: the v1 pair.  Otherwise the no-workspace route
 // (attn_bwd_dq_v2 + attn_bwd_dkdv_v2) when asked for, or when the dS
 // workspace (twice as large with the P workspace of pstore) would exceed the
-// cap; else the workspace route, where pstore and no_tr16 apply.
+// cap; else the workspace route, where pstore and no_tr16 apply.  dk and dv
+// come from the fused kernel unless pstore, no_tr16 or split_dkdv ask for the
+// two passes; split_dkdv stays set in the route only where it alone does.
 AttnBwdRoute attn_bwd_select(const AttnKnobs& knobs, int64_t B, int64_t H,
                              int64_t S, int64_t D) {
-  AttnBwdRoute r{false, false, false, false};
+  AttnBwdRoute r{false, false, false, false, false};
   r.v1 = D != 128 || knobs.force_v1;
   if (r.v1) return r;
   const int64_t spad_est = (S + QT2 - 1) / QT2 * QT2;
   const int64_t pmul = knobs.pstore ? 4 : 2;
   const int64_t ds_bytes = B * H * S * spad_est * pmul;
   r.recompute = knobs.dq_recompute || ds_bytes > knobs.max_ds_bytes;
+  r.split_dkdv = knobs.split_dkdv;
   if (r.recompute) return r;
   r.pstore = knobs.pstore;
   r.no_tr16 = knobs.no_tr16;
+  // pstore and no_tr16 already mean the two-pass kernels
+  if (r.pstore || r.no_tr16) r.split_dkdv = false;
   return r;
 }
 
-// Combined backward: dv pass, dk pass storing dS, dq-lite consuming it.
+// Combined backward: the fused dk/dv kernel storing dS (or, on the two-pass
+// routes, the dv pass and the dk pass storing dS), dq-lite consuming it.
 // route.recompute falls back to the independent recomputing dq kernel
-// (and no dS workspace) for A/B and as an escape hatch.
+// (and no dS workspace) for A/B and as an escape hatch.  skip_dq stops after
+// dk/dv (dS still stored on the workspace route): the kernel A/B's handle on
+// the dk/dv stage alone.
 void attn_bwd_v2_all(torch::Tensor dout, torch::Tensor q, torch::Tensor k,
                      torch::Tensor v, torch::Tensor lse, torch::Tensor delta,
                      torch::Tensor dq, torch::Tensor dk, torch::Tensor dv,
-                     bool causal, double scale, const AttnBwdRoute& route) {
+                     bool causal, double scale, const AttnBwdRoute& route,
+                     bool skip_dq) {
   TORCH_CHECK(!route.v1, "attn_bwd_v2_all: the v1 route is attn_bwd's");
   // The dS-store path buys -13% backward time (r01 v12) at the cost of an
   // O(S^2) bf16 workspace (B*H*S*S_pad).  That grows quadratically with
@@ -1189,8 +1537,15 @@ void attn_bwd_v2_all(torch::Tensor dout, torch::Tensor q, torch::Tensor k,
   // (bound the workspace for the long-context
   // direction).
   if (route.recompute) {
-    attn_bwd_dq_v2(dout, q, k, v, lse, delta, dq, causal, scale);
-    attn_bwd_dkdv_v2(dout, q, k, v, lse, delta, dk, dv, causal, scale);
+    if (!skip_dq) attn_bwd_dq_v2(dout, q, k, v, lse, delta, dq, causal, scale);
+    if (route.two_pass()) {
+      attn_bwd_dkdv_v2(dout, q, k, v, lse, delta, dk, dv, causal, scale);
+    } else {
+      TORCH_CHECK(q.size(3) == 128);
+      launch_dkdv_fused(dout, q, k, v, lse, delta, dk, dv, nullptr, 0, causal,
+                        scale);
+      HIP_CHECK_LAST();
+    }
     return;
   }
   const int B = q.size(0), H = q.size(1), S = q.size(2), D = q.size(3);
@@ -1218,7 +1573,10 @@ void attn_bwd_v2_all(torch::Tensor dout, torch::Tensor q, torch::Tensor k,
     pwt = torch::empty({(long)B * H, spad, spad}, q.options());
     pw = (unsigned short*)pwt.data_ptr();
   }
-  if (causal) {
+  if (!route.two_pass()) {
+    launch_dkdv_fused(dout, q, k, v, lse, delta, dk, dv, dsp, spad, causal,
+                      scale);
+  } else if (causal) {
     if (pw) L_KV2(true, true, dsp, spad, pw, 1, 2);
     else L_KV2(true, true, dsp, spad, nullptr, 0, 0);
   } else {
@@ -1226,6 +1584,10 @@ void attn_bwd_v2_all(torch::Tensor dout, torch::Tensor q, torch::Tensor k,
     else L_KV2(false, true, dsp, spad, nullptr, 0, 0);
   }
 #undef L_KV2
+  if (skip_dq) {
+    HIP_CHECK_LAST();
+    return;
+  }
   const bool no_tr16 = route.no_tr16;
 #define L_DQL(CC)                                                             \
   do {                                                                        \

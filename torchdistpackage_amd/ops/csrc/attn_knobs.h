@@ -7,10 +7,12 @@
 
 struct AttnKnobs {
   bool dq_recompute;     // TDPA_DQ_RECOMPUTE: no-workspace backward
-  bool no_tr16;          // TDPA_NO_TR16: dq-lite without the hardware transpose
+  bool no_tr16;          // TDPA_NO_TR16: no hardware transpose reads in the
+                         // backward: two-pass dk/dv and the scatter dq-lite
   bool pstore;           // TDPA_PSTORE: dv pass stores P for the dk pass
   bool force_v1;         // TDPA_ATTN_V1: head dim 128 through the v1 kernels
   int64_t max_ds_bytes;  // dS (+P) workspace cap; above it: recompute route
+  bool split_dkdv;       // TDPA_SPLIT_DKDV: two-pass dk/dv on every v2 route
 };
 
 AttnKnobs& attn_knobs_ref();   // attention.hip
@@ -19,8 +21,11 @@ AttnKnobs& attn_knobs_ref();   // attention.hip
 // kernels, either the no-workspace recompute route or the dS-workspace route
 // with its two options.  attn_bwd dispatches on this struct and
 // attn_bwd_route() names it, so the name cannot drift from the launch.
+// dk and dv come from the fused kernel unless two_pass(); split_dkdv is set
+// only where that knob alone selects the two passes.
 struct AttnBwdRoute {
-  bool v1, recompute, pstore, no_tr16;
+  bool v1, recompute, pstore, no_tr16, split_dkdv;
+  bool two_pass() const { return pstore || no_tr16 || split_dkdv; }
 };
 
 AttnBwdRoute attn_bwd_select(const AttnKnobs& knobs, int64_t B, int64_t H,

@@ -48,10 +48,10 @@ std::vector<torch::Tensor> attn_bwd(torch::Tensor dout, torch::Tensor q,
                                     torch::Tensor dq, torch::Tensor dk,
                                     torch::Tensor dv,
                                     bool causal, double scale);
-std::tuple<bool, bool, bool, bool, int64_t> attn_knobs();
-std::tuple<bool, bool, bool, bool, int64_t> attn_set_knobs(
+std::tuple<bool, bool, bool, bool, int64_t, bool> attn_knobs();
+std::tuple<bool, bool, bool, bool, int64_t, bool> attn_set_knobs(
     bool dq_recompute, bool no_tr16, bool pstore, bool force_v1,
-    int64_t max_ds_bytes);
+    int64_t max_ds_bytes, bool split_dkdv);
 std::string attn_bwd_route(int64_t B, int64_t H, int64_t S, int64_t D);
 torch::Tensor mfma_probe_16x16x32(torch::Tensor a, torch::Tensor b);
 torch::Tensor mfma_probe_32x32x16(torch::Tensor a, torch::Tensor b);
@@ -109,6 +109,10 @@ torch::Tensor bias_residual_add(torch::Tensor y,
                                 c10::optional<torch::Tensor> bias,
                                 torch::Tensor x_res);
 torch::Tensor attn_delta(torch::Tensor o, torch::Tensor dout);
+void attn_bwd_dkdv(torch::Tensor dout, torch::Tensor q, torch::Tensor k,
+                   torch::Tensor v, torch::Tensor lse, torch::Tensor delta,
+                   torch::Tensor dk, torch::Tensor dv, bool causal,
+                   double scale);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rmsnorm_fwd", &rmsnorm_fwd);
@@ -128,9 +132,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_fwd", &attn_fwd);
   m.def("attn_bwd", &attn_bwd);
   m.def("attn_knobs", &attn_knobs,
-        "(dq_recompute, no_tr16, pstore, force_v1, max_ds_bytes)");
+        "(dq_recompute, no_tr16, pstore, force_v1, max_ds_bytes, split_dkdv)");
   m.def("attn_set_knobs", &attn_set_knobs,
-        "set the five attention knobs; returns the previous five");
+        "set the six attention knobs; returns the previous six");
   m.def("attn_bwd_route", &attn_bwd_route,
         "name of the backward route for (B, H, S, D) under the current knobs");
   m.def("mfma_probe_16x16x32", &mfma_probe_16x16x32);
@@ -174,4 +178,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "(y, bias|None, x_res) -> bf16(x_res + bf16(y + bias))");
   m.def("attn_delta", &attn_delta,
         "(o, dout) (B, H, S, D) bf16 -> rowsum(o * dout) (B, H, S) fp32");
+  m.def("attn_bwd_dkdv", &attn_bwd_dkdv,
+        "(dout, q, k, v, lse, delta, dk, dv, causal, scale): the dk/dv stage "
+        "of the head-dim-128 backward alone, under the current knobs");
 }

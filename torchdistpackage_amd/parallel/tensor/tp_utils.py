@@ -134,6 +134,11 @@ class _ReduceFromTp(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x):
+        # TP size 1: the all-reduce is the identity and nothing is mutated,
+        # so the input goes through (a clone here was a pure 2-pass copy of
+        # every Row-parallel output)
+        if get_tp_size() == 1:
+            return x
         return _all_reduce(x.clone())
 
     @staticmethod
@@ -150,6 +155,8 @@ class _CopyToTp(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad):
+        if get_tp_size() == 1:
+            return grad
         # clone: never mutate the incoming grad in place (all_reduce would)
         return _all_reduce(grad.contiguous().clone())
 
