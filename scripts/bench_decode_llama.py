@@ -2,7 +2,11 @@
 
 ``--int8`` runs the weight-only int8 A/B instead (scripts/_decode_ab.py):
 bf16 against ``quantize_linears_`` weights in the same process, B = 1 and 8
-at max_seq/prompt 192/128 and 4096/2048, ``--attn-impl`` in both arms."""
+at max_seq/prompt 192/128 and 4096/2048, ``--attn-impl`` in both arms.
+
+``--prefill-attn`` runs the prefill-attention A/B (scripts/
+kbench_prefill_attn.py): time to first token at a 2048-token prompt and
+ms/token of speculative decoding, ``TDPA_PREFILL_ATTN`` off against on."""
 import argparse
 import os
 import sys
@@ -20,6 +24,7 @@ dev = torch.device("cuda")
 torch.manual_seed(0)
 ap = argparse.ArgumentParser()
 ap.add_argument("--int8", action="store_true")
+ap.add_argument("--prefill-attn", action="store_true")
 ap.add_argument("--attn-impl", default="hip", choices=("hip", "sdpa"))
 args = ap.parse_args()
 m = LlamaModel(llama3_8b(), device=dev, dtype=torch.bfloat16).eval()
@@ -28,6 +33,12 @@ if args.int8:
     from _decode_ab import int8_ab
     int8_ab(m, GraphedLlamaDecoder, 128256, args.attn_impl, "llama-8b")
     print("LLAMA DECODE INT8 AB OK")
+    sys.exit(0)
+
+if args.prefill_attn:
+    from kbench_prefill_attn import end_to_end
+    end_to_end(m)
+    print("LLAMA PREFILL ATTN AB OK")
     sys.exit(0)
 
 for B in (1, 8):

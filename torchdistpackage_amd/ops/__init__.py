@@ -860,6 +860,91 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor,
     return o4
 
 
+# ---------------------------------------------------------------------------
+# prefill attention over a KV cache (flash-prefill MFMA kernel): the same
+# contract as decode_attention for any number of new rows in one launch
+# ---------------------------------------------------------------------------
+
+# TDPA_PREFILL_ATTN=1 lets the hip cached-attention route send chunks of more
+# than _DECODE_MAX_ROWS rows per kv head to prefill_attention (read once, here)
+_PREFILL_ATTN = os.environ.get("TDPA_PREFILL_ATTN", "0") == "1"
+
+_PREFILL_MAX_GROUP = 16   # query heads per kv head the kernel serves
+
+
+def prefill_attention_enabled() -> bool:
+    return _PREFILL_ATTN
+
+
+def set_prefill_attention(on: bool) -> bool:
+    """Switch the prefill-attention routing of the hip cached-attention
+    route on or off for this process; returns the previous setting.  For
+    tests and same-process A/B runs."""
+    global _PREFILL_ATTN
+    prev, _PREFILL_ATTN = _PREFILL_ATTN, bool(on)
+    return prev
+
+
+def prefill_attention(q: torch.Tensor, k_cache: torch.Tensor,
+                      v_cache: torch.Tensor, pos0, scale: float = None,
+                      pos_tile: Optional[int] = None) -> torch.Tensor:
+    """Causal attention of ``Sq`` new query rows against a KV cache, any
+    ``Sq`` in one launch (prompt prefill, chunked prefill, speculative
+    verification).
+
+    Shapes, ``pos0`` forms (host int, or int64 tensor of 1 or B elements
+    read on the device), errors and the returned layout are those of
+    :func:`decode_attention`: row ``i`` of batch ``b`` sees cache positions
+    ``[0, pos_b + i]``, nothing at or beyond ``pos_b + Sq`` reaches the
+    result, and the (B, Hq, Sq, D) result is a strided view of an
+    (Sq, B, Hq*D) buffer.  A tensor ``pos0`` works at any ``Sq``.
+
+    GPU bf16 runs the flash-prefill HIP kernel (head dim 64 or 128,
+    ``Hq/Hkv <= 16``; anything else raises — there is no composite path).
+    CPU tensors of any float dtype run exact fp32 math (the oracle).
+    ``pos_tile`` overrides the workgroup's position-tile length, in 16-row
+    wave tiles (tests; default chosen from the shapes and the CU count).
+    """
+    B, Hq, Sq, D = q.shape
+    Hkv = k_cache.shape[1]
+    if Hq % Hkv != 0:
+        raise ValueError(f"prefill_attention: Hq={Hq} not a multiple of "
+                         f"Hkv={Hkv}")
+    if scale is None:
+        scale = 1.0 / math.sqrt(D)
+    if not q.is_cuda:
+        o = _decode_attention_ref(q, k_cache, v_cache, pos0, scale)
+        o_buf = o.permute(2, 0, 1, 3).contiguous()      # (Sq, B, Hq, D)
+        return o_buf.permute(1, 2, 0, 3)
+    if q.dtype != torch.bfloat16:
+        raise TypeError("prefill_attention: the GPU kernel is bf16-only, got "
+                        f"{q.dtype}")
+    if D not in (64, 128):
+        raise ValueError("prefill_attention: the GPU kernel covers head dim "
+                         f"64 and 128, got {D}")
+    if Hq // Hkv > _PREFILL_MAX_GROUP:
+        raise ValueError(f"prefill_attention: Hq/Hkv={Hq // Hkv} exceeds the "
+                         f"kernel's {_PREFILL_MAX_GROUP} heads per kv head")
+    if Sq < 1 or Sq > k_cache.shape[2]:
+        raise ValueError(f"prefill_attention: Sq={Sq} outside the cache "
+                         f"(Smax={k_cache.shape[2]})")
+    e = ext("prefill_attention")
+    o_buf = torch.empty(Sq, B, Hq * D, dtype=q.dtype, device=q.device)
+    o4 = o_buf.view(Sq, B, Hq, D).permute(1, 2, 0, 3)
+    ptw = int(pos_tile or 0)
+    if torch.is_tensor(pos0):
+        e.prefill_attention(q, k_cache, v_cache, o4, pos0, 0, float(scale),
+                            ptw)
+        return o4
+    pos0 = int(pos0)
+    if pos0 < 0 or pos0 + Sq > k_cache.shape[2]:
+        raise ValueError(f"prefill_attention: pos0={pos0} with Sq={Sq} "
+                         f"outside the cache (Smax={k_cache.shape[2]})")
+    e.prefill_attention(q, k_cache, v_cache, o4, None, pos0, float(scale),
+                        ptw)
+    return o4
+
+
 class _CrossEntropyFn(torch.autograd.Function):
     """Fused mean cross-entropy on bf16 logits (one online-LSE pass fwd, one
     dlogits pass bwd) — replaces logits.float()+F.cross_entropy which

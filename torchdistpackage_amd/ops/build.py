@@ -29,6 +29,7 @@ SOURCES = [
     "gemv.hip",
     "gemv_int8.hip",
     "decode_attn.hip",
+    "prefill_attn.hip",
     "grouped_gemm.hip",
 ]
 

@@ -85,6 +85,10 @@ torch::Tensor decode_attention(torch::Tensor q, torch::Tensor k_cache,
                                torch::Tensor v_cache, torch::Tensor out,
                                c10::optional<torch::Tensor> pos_t, long pos0,
                                double scale, long split_kv);
+torch::Tensor prefill_attention(torch::Tensor q, torch::Tensor k_cache,
+                                torch::Tensor v_cache, torch::Tensor out,
+                                c10::optional<torch::Tensor> pos_t, long pos0,
+                                double scale, long pos_tile);
 torch::Tensor grouped_gemm_fprop(torch::Tensor x, torch::Tensor w,
                                  torch::Tensor offs,
                                  c10::optional<torch::Tensor> bias);
@@ -155,6 +159,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemv_w8a16", &gemv_w8a16);
   m.def("rope_apply_pos", &rope_apply_pos);
   m.def("decode_attention", &decode_attention);
+  m.def("prefill_attention", &prefill_attention,
+        "(q, k_cache, v_cache, out, pos_t|None, pos0, scale, pos_tile) -> out");
   m.def("grouped_gemm_fprop", &grouped_gemm_fprop);
   m.def("grouped_gemm_dgrad", &grouped_gemm_dgrad);
   m.def("grouped_gemm_wgrad", &grouped_gemm_wgrad);

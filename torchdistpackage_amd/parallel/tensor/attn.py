@@ -44,6 +44,15 @@ def _cached_sdpa(q: torch.Tensor, k_cache: torch.Tensor,
     return F.scaled_dot_product_attention(q, ka, va, attn_mask=mask)
 
 
+# Rows per kv head (G * S) above which the hip route, with TDPA_PREFILL_ATTN
+# on, sends a host-int-pos0 chunk to ops.prefill_attention.  Measured, not
+# the 16 rows of one decode_attention launch: without split-KV a short chunk
+# is a handful of workgroups walking the whole cache, and row-blocked
+# decode_attention still wins up to 64 rows at batch 1 (docs/design/
+# inference.md "Prefill attention" has the table).
+_PREFILL_MIN_ROWS = 64
+
+
 def _cached_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
                       k_cache: torch.Tensor, v_cache: torch.Tensor, pos0,
                       causal: bool, attn_impl: Optional[str] = None,
@@ -65,6 +74,9 @@ def _cached_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
 
     ``attn_impl="hip"`` runs ops.decode_attention on the un-expanded caches
     with either form; the SDPA routes expand K/V heads to Q heads first.
+    With ``TDPA_PREFILL_ATTN`` on, a host-int chunk of more than
+    ``_PREFILL_MIN_ROWS`` rows per kv head runs ops.prefill_attention instead
+    (one launch, where decode_attention would loop on the host).
     """
     B, H, S, hd = q.shape
     hip = resolve_decode_attn_impl(attn_impl) == "hip"
@@ -84,7 +96,12 @@ def _cached_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     if hip:
         assert causal or S == 1, \
             "decode_attention is causal over the new rows"
-        o = ops.decode_attention(q, k_cache, v_cache, pos0)
+        G = H // k_cache.shape[1]
+        if (not on_device and ops.prefill_attention_enabled()
+                and G * S > _PREFILL_MIN_ROWS):
+            o = ops.prefill_attention(q, k_cache, v_cache, pos0)
+        else:
+            o = ops.decode_attention(q, k_cache, v_cache, pos0)
     else:
         rep = H // k_cache.shape[1]
         if rep != 1:
