@@ -32,7 +32,12 @@ cfg = gpt2_xl_1p3b()
 ap = argparse.ArgumentParser()
 ap.add_argument("--int8", action="store_true")
 ap.add_argument("--attn-impl", default="hip", choices=("hip", "sdpa"))
+ap.add_argument("--kv-fp8", action="store_true",
+                help="fp8 KV caches (ops.Fp8KV) on the hip route")
 args = ap.parse_args()
+# fp8 caches need the hip route; otherwise the defaults (TDPA_DECODE_ATTN)
+KV = {"attn_impl": "hip", "kv_dtype": "fp8"} if args.kv_fp8 else {}
+IMPL = KV.get("attn_impl")
 if args.int8:
     from torchdistpackage_amd.inference.generate import GraphedGPT2Decoder
     from _decode_ab import int8_ab
@@ -44,12 +49,12 @@ if args.int8:
     sys.exit(0)
 m = GPT2Model(cfg, device=dev, dtype=torch.bfloat16).eval()
 idx = torch.randint(0, cfg.vocab_size, (B, PROMPT), device=dev)
-caches = _alloc_caches(m, B, PROMPT + NEW)
+caches = _alloc_caches(m, B, PROMPT + NEW, KV.get("kv_dtype"))
 
 with torch.no_grad():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    logits = decode_forward(m, idx, caches, 0)
+    logits = decode_forward(m, idx, caches, 0, attn_impl=IMPL)
     torch.cuda.synchronize()
     t_prefill = time.perf_counter() - t0
 
@@ -57,14 +62,14 @@ with torch.no_grad():
     pos0 = PROMPT
     # warmup decode steps
     for _ in range(8):
-        logits = decode_forward(m, nxt, caches, pos0)
+        logits = decode_forward(m, nxt, caches, pos0, attn_impl=IMPL)
         nxt = logits.argmax(-1)[:, None]
         pos0 += 1
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     n_timed = NEW - 8
     for _ in range(n_timed):
-        logits = decode_forward(m, nxt, caches, pos0)
+        logits = decode_forward(m, nxt, caches, pos0, attn_impl=IMPL)
         nxt = logits.argmax(-1)[:, None]
         pos0 += 1
     torch.cuda.synchronize()
@@ -77,7 +82,7 @@ print(f"eager decode: {dt/n_timed*1e3:.2f} ms/step, "
 
 from torchdistpackage_amd.inference.generate import GraphedGPT2Decoder
 
-dec = GraphedGPT2Decoder(m, batch=B, max_seq=PROMPT + NEW)
+dec = GraphedGPT2Decoder(m, batch=B, max_seq=PROMPT + NEW, **KV)
 dec.prefill(idx)
 for _ in range(8):
     dec.step()
@@ -92,7 +97,7 @@ print(f"graphed decode: {dt/n_timed*1e3:.2f} ms/step, "
 
 if B1:
     idx1 = idx[:1]
-    dec1 = GraphedGPT2Decoder(m, batch=1, max_seq=PROMPT + NEW)
+    dec1 = GraphedGPT2Decoder(m, batch=1, max_seq=PROMPT + NEW, **KV)
     dec1.prefill(idx1)
     for _ in range(8):
         dec1.step()

@@ -6,7 +6,11 @@ at max_seq/prompt 192/128 and 4096/2048, ``--attn-impl`` in both arms.
 
 ``--prefill-attn`` runs the prefill-attention A/B (scripts/
 kbench_prefill_attn.py): time to first token at a 2048-token prompt and
-ms/token of speculative decoding, ``TDPA_PREFILL_ATTN`` off against on."""
+ms/token of speculative decoding, ``TDPA_PREFILL_ATTN`` off against on.
+
+``--kv-fp8`` runs the fp8 KV cache A/B (scripts/kbench_decode_attn_fp8.py):
+bf16 cache against fp8 cache on the hip route, ms/token, time to first token
+and resident cache bytes."""
 import argparse
 import os
 import sys
@@ -25,6 +29,7 @@ torch.manual_seed(0)
 ap = argparse.ArgumentParser()
 ap.add_argument("--int8", action="store_true")
 ap.add_argument("--prefill-attn", action="store_true")
+ap.add_argument("--kv-fp8", action="store_true")
 ap.add_argument("--attn-impl", default="hip", choices=("hip", "sdpa"))
 args = ap.parse_args()
 m = LlamaModel(llama3_8b(), device=dev, dtype=torch.bfloat16).eval()
@@ -39,6 +44,12 @@ if args.prefill_attn:
     from kbench_prefill_attn import end_to_end
     end_to_end(m)
     print("LLAMA PREFILL ATTN AB OK")
+    sys.exit(0)
+
+if args.kv_fp8:
+    from kbench_decode_attn_fp8 import end_to_end
+    end_to_end(m)
+    print("LLAMA KV FP8 AB OK")
     sys.exit(0)
 
 for B in (1, 8):

@@ -17,22 +17,40 @@ ops.decode_attention).  ``None`` reads ``TDPA_DECODE_ATTN``.
 
 from __future__ import annotations
 
+import os
 from typing import List, Optional, Tuple
 
 import torch
 
-from ..ops import resolve_decode_attn_impl
+from ..ops import Fp8KV, resolve_decode_attn_impl
 from ..parallel.tensor import get_tp_size
 
 
-def _alloc_caches(model, batch: int,
-                  max_seq: int) -> List[Tuple[torch.Tensor, torch.Tensor]]:
+def resolve_kv_dtype(kv_dtype: Optional[str] = None) -> str:
+    """``"bf16"`` (caches in the model's dtype, the default) or ``"fp8"``
+    (ops.Fp8KV caches: e4m3 bytes and a power-of-two scale per row; needs
+    ``attn_impl="hip"``).  ``None`` reads ``TDPA_KV_DTYPE``."""
+    if kv_dtype is None:
+        kv_dtype = os.environ.get("TDPA_KV_DTYPE", "bf16")
+    if kv_dtype not in ("bf16", "fp8"):
+        raise ValueError(f"kv_dtype must be 'bf16' or 'fp8', got "
+                         f"{kv_dtype!r}")
+    return kv_dtype
+
+
+def _alloc_caches(model, batch: int, max_seq: int,
+                  kv_dtype: Optional[str] = None) -> List[Tuple]:
     """Zeroed per-layer (k, v) caches (B, n_kv, max_seq, hd) for ``model``,
-    on its parameters' device and dtype."""
+    on its parameters' device: tensors of its dtype, or with
+    ``kv_dtype="fp8"`` pairs of ops.Fp8KV."""
     cfg = model.cfg
     p = next(model.parameters())
     shape = (batch, getattr(cfg, "n_kv_head", cfg.n_head), max_seq,
              cfg.dim // cfg.n_head)
+    if resolve_kv_dtype(kv_dtype) == "fp8":
+        return [(Fp8KV.zeros(*shape, device=p.device),
+                 Fp8KV.zeros(*shape, device=p.device))
+                for _ in range(cfg.n_layer)]
     return [(torch.zeros(shape, device=p.device, dtype=p.dtype),
              torch.zeros(shape, device=p.device, dtype=p.dtype))
             for _ in range(cfg.n_layer)]
@@ -86,6 +104,9 @@ class GraphedDecoder:
     valid length instead of the cache capacity, GQA caches are read
     un-expanded, and no mask is built or maintained.
 
+    ``kv_dtype="fp8"`` (hip route only) keeps the caches as ops.Fp8KV; the
+    quantising cache write is captured with the step.
+
     Greedy only (the argmax lives inside the graph).  Works for either
     model family (``GraphedGPT2Decoder`` and ``GraphedLlamaDecoder`` are
     this class); usage::
@@ -95,7 +116,8 @@ class GraphedDecoder:
     """
 
     def __init__(self, model, batch: int, max_seq: int, warmup: int = 3,
-                 attn_impl: Optional[str] = None):
+                 attn_impl: Optional[str] = None,
+                 kv_dtype: Optional[str] = None):
         assert get_tp_size() == 1
         self.attn_impl = resolve_decode_attn_impl(attn_impl)
         assert torch.cuda.is_available()
@@ -104,7 +126,7 @@ class GraphedDecoder:
         p = next(model.parameters())
         dev, dtype = p.device, p.dtype
         self.max_seq = max_seq
-        self.caches = _alloc_caches(model, batch, max_seq)
+        self.caches = _alloc_caches(model, batch, max_seq, kv_dtype)
         self.in_tok = torch.zeros(batch, 1, dtype=torch.long, device=dev)
         self.pos_t = torch.zeros(1, dtype=torch.long, device=dev)
         self.pos = 0
@@ -180,7 +202,8 @@ GraphedGPT2Decoder = GraphedLlamaDecoder = GraphedDecoder
 def generate(model, idx: torch.Tensor, max_new_tokens: int,
              greedy: bool = True, temperature: float = 1.0,
              top_k: Optional[int] = None,
-             attn_impl: Optional[str] = None) -> torch.Tensor:
+             attn_impl: Optional[str] = None,
+             kv_dtype: Optional[str] = None) -> torch.Tensor:
     """Autoregressive generation with KV caches.
 
     Args:
@@ -189,13 +212,16 @@ def generate(model, idx: torch.Tensor, max_new_tokens: int,
         max_new_tokens: number of tokens to append.
         attn_impl: decode attention, ``"sdpa"`` or ``"hip"``; ``None``
             reads ``TDPA_DECODE_ATTN`` (default sdpa).
+        kv_dtype: KV cache format, ``"bf16"`` (the model's dtype) or
+            ``"fp8"`` (needs ``attn_impl="hip"``); ``None`` reads
+            ``TDPA_KV_DTYPE`` (default bf16).
     Returns (B, S0 + max_new_tokens) token ids.
     """
     assert get_tp_size() == 1, "generate() supports tp=1 (single device)"
     B, S0 = idx.shape
     total = S0 + max_new_tokens
     assert total <= model.cfg.max_seq, (total, model.cfg.max_seq)
-    caches = _alloc_caches(model, B, total)
+    caches = _alloc_caches(model, B, total, kv_dtype)
 
     tokens = idx
     chunk, pos0 = idx, 0
@@ -212,7 +238,8 @@ def generate(model, idx: torch.Tensor, max_new_tokens: int,
 @torch.no_grad()
 def speculative_generate(target, draft, idx: torch.Tensor,
                          max_new_tokens: int, k: int = 4,
-                         attn_impl: Optional[str] = None) -> torch.Tensor:
+                         attn_impl: Optional[str] = None,
+                         kv_dtype: Optional[str] = None) -> torch.Tensor:
     """Greedy speculative decoding: ``draft`` proposes ``k`` tokens per
     round, ``target`` verifies the whole chunk in ONE forward.  Output is
     EXACTLY the target's greedy generation — the draft only changes how
@@ -221,7 +248,8 @@ def speculative_generate(target, draft, idx: torch.Tensor,
     Cache bookkeeping: rejected proposals leave stale entries past the
     committed length in both caches; they are overwritten sequentially
     before any later position can attend to them, so a rollback is just a
-    smaller next ``pos0``.  B=1 (speculative decode is per-request —
+    smaller next ``pos0`` (with ``kv_dtype="fp8"`` too: a row's scale is
+    overwritten with its bytes).  B=1 (speculative decode is per-request —
     batched rows would accept different lengths each round).
     """
     assert get_tp_size() == 1
@@ -229,8 +257,8 @@ def speculative_generate(target, draft, idx: torch.Tensor,
     S0 = idx.shape[1]
     cap = S0 + max_new_tokens + k + 1
     assert cap <= target.cfg.max_seq and cap <= draft.cfg.max_seq
-    t_caches = _alloc_caches(target, 1, cap)
-    d_caches = _alloc_caches(draft, 1, cap)
+    t_caches = _alloc_caches(target, 1, cap, kv_dtype)
+    d_caches = _alloc_caches(draft, 1, cap, kv_dtype)
     attn_impl = resolve_decode_attn_impl(attn_impl)
     lt = decode_forward(target, idx, t_caches, 0, attn_impl=attn_impl)
     decode_forward(draft, idx, d_caches, 0, attn_impl=attn_impl)

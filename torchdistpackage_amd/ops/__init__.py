@@ -814,6 +814,11 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor,
     else raises — there is no composite path).  CPU tensors of any float
     dtype run exact fp32 math (the oracle).  ``split_kv`` overrides the KV
     chunk length per workgroup (tests; default chosen from Smax).
+
+    The caches may be a pair of :class:`Fp8KV` (e4m3 bytes and a scale per
+    row, written by :func:`kv_cache_append`): the GPU runs the fp8 variant
+    of the kernel under the same contract, the CPU dequantises (exactly)
+    and runs the oracle.  One Fp8KV and one tensor raise.
     """
     B, Hq, Sq, D = q.shape
     Hkv = k_cache.shape[1]
@@ -822,6 +827,14 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor,
                          f"Hkv={Hkv}")
     if scale is None:
         scale = 1.0 / math.sqrt(D)
+    fp8 = isinstance(k_cache, Fp8KV)
+    if fp8 != isinstance(v_cache, Fp8KV):
+        raise TypeError("decode_attention: k_cache and v_cache must both be "
+                        "Fp8KV or both be tensors")
+    if fp8 and not q.is_cuda:
+        # the oracle attends to the dequantised values, exact in fp32
+        k_cache = k_cache.dequantize(torch.float32)
+        v_cache = v_cache.dequantize(torch.float32)
     if not q.is_cuda:
         o = _decode_attention_ref(q, k_cache, v_cache, pos0, scale)
         o_buf = o.permute(2, 0, 1, 3).contiguous()      # (Sq, B, Hq, D)
@@ -840,6 +853,16 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor,
     o_buf = torch.empty(Sq, B, Hq * D, dtype=q.dtype, device=q.device)
     o4 = o_buf.view(Sq, B, Hq, D).permute(1, 2, 0, 3)
     skv = int(split_kv or 0)
+    if fp8:
+        # the fp8 kernel (csrc/decode_attn_fp8.hip) behind the same calls
+        def launch(q_, o_, pos_t, p0):
+            e.decode_attention_fp8(q_, k_cache.data, k_cache.scale,
+                                   v_cache.data, v_cache.scale, o_, pos_t,
+                                   p0, float(scale), skv)
+    else:
+        def launch(q_, o_, pos_t, p0):
+            e.decode_attention(q_, k_cache, v_cache, o_, pos_t, p0,
+                               float(scale), skv)
     if torch.is_tensor(pos0):
         if G * Sq > _DECODE_MAX_ROWS:
             raise ValueError(
@@ -847,16 +870,13 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor,
                 f"{_DECODE_MAX_ROWS} rows per kv head; with a tensor pos0 "
                 "the call cannot be split on the host — pass an int pos0 "
                 "or fewer query rows")
-        e.decode_attention(q, k_cache, v_cache, o4, pos0, 0, float(scale),
-                           skv)
+        launch(q, o4, pos0, 0)
         return o4
     pos0 = int(pos0)
     rows = _DECODE_MAX_ROWS // G          # query rows per kernel call
     for r0 in range(0, Sq, rows):
         r1 = min(r0 + rows, Sq)
-        e.decode_attention(q[:, :, r0:r1], k_cache, v_cache,
-                           o4[:, :, r0:r1], None, pos0 + r0, float(scale),
-                           skv)
+        launch(q[:, :, r0:r1], o4[:, :, r0:r1], None, pos0 + r0)
     return o4
 
 
@@ -1123,3 +1143,10 @@ from .grouped import (GROUPED_GEMM_BM, grouped_gemm_eligible,  # noqa: E402
 
 from .int8 import (Int8Weight, int8_linear, quantize_int8,  # noqa: E402
                    quantize_linears_)
+
+# ---------------------------------------------------------------------------
+# fp8 (e4m3) KV cache: cache type, quantising append, dequantise; read by
+# decode_attention above
+# ---------------------------------------------------------------------------
+
+from .kv_fp8 import Fp8KV, kv_cache_append, quantize_kv_rows  # noqa: E402

@@ -29,6 +29,8 @@ SOURCES = [
     "gemv.hip",
     "gemv_int8.hip",
     "decode_attn.hip",
+    "decode_attn_fp8.hip",
+    "kv_fp8.hip",
     "prefill_attn.hip",
     "grouped_gemm.hip",
 ]

@@ -89,6 +89,18 @@ torch::Tensor prefill_attention(torch::Tensor q, torch::Tensor k_cache,
                                 torch::Tensor v_cache, torch::Tensor out,
                                 c10::optional<torch::Tensor> pos_t, long pos0,
                                 double scale, long pos_tile);
+torch::Tensor decode_attention_fp8(torch::Tensor q, torch::Tensor k_data,
+                                   torch::Tensor k_scale,
+                                   torch::Tensor v_data,
+                                   torch::Tensor v_scale, torch::Tensor out,
+                                   c10::optional<torch::Tensor> pos_t,
+                                   long pos0, double scale, long split_kv);
+void kv_fp8_append(torch::Tensor k_data, torch::Tensor k_scale,
+                   torch::Tensor v_data, torch::Tensor v_scale,
+                   torch::Tensor k, torch::Tensor v,
+                   c10::optional<torch::Tensor> pos_t, long pos0);
+torch::Tensor kv_fp8_dequant(torch::Tensor data, torch::Tensor scale,
+                             long length, bool to_bf16);
 torch::Tensor grouped_gemm_fprop(torch::Tensor x, torch::Tensor w,
                                  torch::Tensor offs,
                                  c10::optional<torch::Tensor> bias);
@@ -161,6 +173,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("decode_attention", &decode_attention);
   m.def("prefill_attention", &prefill_attention,
         "(q, k_cache, v_cache, out, pos_t|None, pos0, scale, pos_tile) -> out");
+  m.def("decode_attention_fp8", &decode_attention_fp8,
+        "(q, k_data, k_scale, v_data, v_scale, out, pos_t|None, pos0, scale, "
+        "split_kv) -> out");
+  m.def("kv_fp8_append", &kv_fp8_append,
+        "(k_data, k_scale, v_data, v_scale, k, v, pos_t|None, pos0)");
+  m.def("kv_fp8_dequant", &kv_fp8_dequant,
+        "(data, scale, length, to_bf16) -> (B, Hkv, length, D) bf16 | fp32");
   m.def("grouped_gemm_fprop", &grouped_gemm_fprop);
   m.def("grouped_gemm_dgrad", &grouped_gemm_dgrad);
   m.def("grouped_gemm_wgrad", &grouped_gemm_wgrad);

@@ -27,40 +27,7 @@
 
 #include <cmath>
 
-#include "common.h"
-
-#define DA_BLOCK 256
-#define DA_WAVES (DA_BLOCK / WAVE)
-#define DA_MAX_M 16
-
-typedef short da_sv2 __attribute__((ext_vector_type(2)));
-
-template <int CTRL>
-DEVINL float da_dpp_add(float v) {
-  const int t = __builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF,
-                                            0xF, false);
-  return v + __int_as_float(t);
-}
-
-// all-reduce sum over aligned groups of LPK (8 or 16) lanes, VALU only
-template <int LPK>
-DEVINL float da_group_sum(float v) {
-  if (LPK == 16) v = da_dpp_add<0x140>(v);  // row_mirror: i <-> 15-i
-  v = da_dpp_add<0x141>(v);                 // row_half_mirror: i <-> 7-i
-  v = da_dpp_add<0xB1>(v);                  // quad_perm [1,0,3,2]
-  v = da_dpp_add<0x4E>(v);                  // quad_perm [2,3,0,1]
-  return v;
-}
-
-DEVINL int da_read_pos(const long* pos_ptr, int pos_stride, long pos_host,
-                       int b, int Smax, int Sq) {
-  long p = pos_ptr ? pos_ptr[(long)b * pos_stride] : pos_host;
-  // clamp BEFORE any address is formed: a stale position tensor may give a
-  // wrong answer, never an out-of-range read
-  const long hi = (long)Smax - Sq;
-  p = p < 0 ? 0 : (p > hi ? hi : p);
-  return (int)p;
-}
+#include "decode_attn_common.h"
 
 template <int D, int MT>
 __global__ __launch_bounds__(DA_BLOCK) void decode_attn_kernel(
@@ -278,30 +245,8 @@ __global__ __launch_bounds__(D) void decode_attn_combine_kernel(
     ushort* __restrict__ out, const long* __restrict__ pos_ptr,
     int pos_stride, long pos_host, int Hkv, int G, int Sq, int Smax,
     int chunk, int nsplit, int MT, long o_sb, long o_sh, long o_ss) {
-  const int bh = blockIdx.x, m = blockIdx.y, d = threadIdx.x;
-  const int b = bh / Hkv, h = bh % Hkv;
-  const int p0 = da_read_pos(pos_ptr, pos_stride, pos_host, b, Smax, Sq);
-  const int len = p0 + Sq;
-  const int nvalid = min(nsplit, (len + chunk - 1) / chunk);
-  const long row0 = (long)bh * nsplit * MT + m;
-  // the loads of different splits are independent: unroll so that several
-  // are in flight (a serial chain of nsplit misses dominated at batch 1)
-  float mx = -INFINITY;
-#pragma unroll 8
-  for (int s = 0; s < nvalid; ++s)
-    mx = fmaxf(mx, part_ml[(row0 + (long)s * MT) * 2]);
-  // split 0 always holds key 0, which every row sees, so mx is finite
-  float l = 0.f, a = 0.f;
-#pragma unroll 8
-  for (int s = 0; s < nvalid; ++s) {
-    const long row = row0 + (long)s * MT;
-    const float f = __builtin_amdgcn_exp2f(part_ml[row * 2] - mx);
-    l += part_ml[row * 2 + 1] * f;
-    a += part_acc[row * D + d] * f;
-  }
-  const int gq = m / Sq, i = m % Sq;
-  out[(long)b * o_sb + (long)(h * G + gq) * o_sh + (long)i * o_ss + d] =
-      f2bf(a / l);
+  da_combine<D>(part_acc, part_ml, out, pos_ptr, pos_stride, pos_host, Hkv, G,
+                Sq, Smax, chunk, nsplit, MT, o_sb, o_sh, o_ss);
 }
 
 static void da_check_kv(const torch::Tensor& t, const char* name) {
@@ -364,14 +309,9 @@ torch::Tensor decode_attention(torch::Tensor q, torch::Tensor k_cache,
 
   // split choice from Smax only, so a captured grid stays valid
   const int BH = B * Hkv;
-  int chunk;
-  if (split_kv > 0) {
-    chunk = (int)std::min<long>((split_kv + 63) / 64 * 64, 1L << 30);
-  } else {
-    const int cus = at::cuda::getCurrentDeviceProperties()->multiProcessorCount;
-    const int want = std::max(1, (2 * cus + BH - 1) / BH);
-    chunk = ((Smax + want - 1) / want + 63) / 64 * 64;
-  }
+  const int chunk = da_choose_chunk(
+      Smax, BH, split_kv,
+      at::cuda::getCurrentDeviceProperties()->multiProcessorCount);
   const int nsplit = (Smax + chunk - 1) / chunk;
   TORCH_CHECK(nsplit <= 65535);
 

@@ -77,10 +77,20 @@ def _cached_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     With ``TDPA_PREFILL_ATTN`` on, a host-int chunk of more than
     ``_PREFILL_MIN_ROWS`` rows per kv head runs ops.prefill_attention instead
     (one launch, where decode_attention would loop on the host).
+
+    The caches may be a pair of ops.Fp8KV (hip route only): the write is
+    ops.kv_cache_append (one quantising launch for K and V, either ``pos0``
+    form), decode_attention runs its fp8 kernel, and a chunk that goes to
+    prefill_attention reads a transient bf16 copy of the visible prefix.
     """
     B, H, S, hd = q.shape
     hip = resolve_decode_attn_impl(attn_impl) == "hip"
     on_device = torch.is_tensor(pos0)
+    fp8 = isinstance(k_cache, ops.Fp8KV) or isinstance(v_cache, ops.Fp8KV)
+    if fp8 and not hip:
+        raise ValueError("fp8 KV caches need attn_impl='hip' "
+                         "(ops.decode_attention reads them); attn_impl="
+                         "'sdpa' has no fp8 path")
     if on_device:
         if S != 1:
             raise ValueError(f"tensor pos0 is the single-token step, got "
@@ -88,6 +98,9 @@ def _cached_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
         if not hip and mask is None:
             raise ValueError("tensor pos0 with attn_impl='sdpa' needs the "
                              "cache visibility mask")
+    if fp8:
+        ops.kv_cache_append(k_cache, v_cache, k, v, pos0)
+    elif on_device:
         k_cache.index_copy_(2, pos0, k)
         v_cache.index_copy_(2, pos0, v)
     else:
@@ -99,6 +112,12 @@ def _cached_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
         G = H // k_cache.shape[1]
         if (not on_device and ops.prefill_attention_enabled()
                 and G * S > _PREFILL_MIN_ROWS):
+            if fp8:
+                # no fp8 arm in the prefill kernel: it reads a transient
+                # bf16 copy of the visible prefix (the same values the fp8
+                # decode kernel attends to)
+                k_cache = k_cache.dequantize(torch.bfloat16, pos0 + S)
+                v_cache = v_cache.dequantize(torch.bfloat16, pos0 + S)
             o = ops.prefill_attention(q, k_cache, v_cache, pos0)
         else:
             o = ops.decode_attention(q, k_cache, v_cache, pos0)
