@@ -1,7 +1,8 @@
 """Same-process A/B of graphed decode, bf16 weights against int8 weights
-(ops.quantize_linears_), shared by bench_decode.py and bench_decode_llama.py.
+(ops.quantize_linears_), shared by bench_decode.py and bench_decode_llama.py;
+``bits=(8, 4)`` adds an int4 arm under the same method.
 
-Both decoders are alive in the same process; the arms alternate for three
+All decoders are alive in the same process; the arms alternate for three
 repeats, a figure is the median ms/token and the spread is the largest
 (max-min)/min of an arm.  ``attn_impl`` is the same in both arms."""
 import copy
@@ -39,16 +40,22 @@ def all_bytes(model):
 
 
 @torch.no_grad()
-def int8_ab(model, Dec, vocab, attn_impl, label):
+def weights_ab(model, Dec, vocab, attn_impl, label, bits=(8,)):
+    """bf16 against one quantised arm per entry of ``bits``, all alive in
+    one process.  Bar (b): the last arm's ms/token is lower than the arm
+    before it by more than the larger repeat spread of the two."""
     from torchdistpackage_amd.ops import quantize_linears_
-    m8 = copy.deepcopy(model)
-    n = quantize_linears_(m8)
-    print(f"## {label}: graphed decode, bf16 vs int8 weights ({n} linears "
-          f"converted), attn_impl={attn_impl}, 3 alternating repeats")
-    for tag, m in (("bf16", model), ("int8", m8)):
+    arms = {"bf16": model}
+    for b in bits:
+        arms[f"int{b}"] = copy.deepcopy(model)
+        n = quantize_linears_(arms[f"int{b}"], bits=b)
+        print(f"int{b}: {n} linears converted")
+    new, old = list(arms)[-1], list(arms)[-2]
+    print(f"## {label}: graphed decode, {' vs '.join(arms)} weights, "
+          f"attn_impl={attn_impl}, 3 alternating repeats")
+    for tag, m in arms.items():
         print(f"resident {tag}: linears {linear_bytes(m) / 1e9:.3f} GB, "
               f"whole model {all_bytes(m) / 1e9:.3f} GB")
-    arms = {"bf16": model, "int8": m8}
     misses = []
     for max_seq, prompt, B in POINTS:
         if max_seq > model.cfg.max_seq:
@@ -77,16 +84,14 @@ def int8_ab(model, Dec, vocab, attn_impl, label):
         del decs
         torch.cuda.empty_cache()
         med = {k: statistics.median(v) for k, v in times.items()}
-        spread = max((max(v) - min(v)) / min(v) for v in times.values())
-        ok = med["int8"] < med["bf16"] * (1 - spread)
-        if not ok:
+        spr = {k: (max(v) - min(v)) / min(v) for k, v in times.items()}
+        if not med[new] < med[old] * (1 - max(spr[new], spr[old])):
             misses.append((max_seq, prompt, B))
-        print(f"max_seq={max_seq} prompt={prompt} B={B}: "
-              f"bf16 {[f'{t:.3f}' for t in times['bf16']]} "
-              f"int8 {[f'{t:.3f}' for t in times['int8']]} "
-              f"median bf16 {med['bf16']:.3f} int8 {med['int8']:.3f} ms/token "
-              f"(int8/bf16 {med['int8'] / med['bf16']:.3f}, "
-              f"spread {100 * spread:.1f}%)", flush=True)
-    print(f"{label} bar (b) (int8 ms/token lower than bf16 by more than the "
-          "repeat spread at every point): "
+        print(f"max_seq={max_seq} prompt={prompt} B={B}: median ms/token "
+              + " ".join(f"{k} {med[k]:.3f} (spread {100 * spr[k]:.1f}%)"
+                         for k in arms)
+              + "; " + " ".join(f"{new}/{k} {med[new] / med[k]:.3f}"
+                                for k in arms if k != new), flush=True)
+    print(f"{label} bar (b) ({new} ms/token lower than {old} by more than "
+          "the repeat spread at every point): "
           + ("MET" if not misses else f"MISSED at {misses}"), flush=True)

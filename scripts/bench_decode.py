@@ -31,6 +31,8 @@ torch.manual_seed(0)
 cfg = gpt2_xl_1p3b()
 ap = argparse.ArgumentParser()
 ap.add_argument("--int8", action="store_true")
+ap.add_argument("--int4", action="store_true",
+                help="the int8 A/B with an int4 arm (bits=4) added")
 ap.add_argument("--attn-impl", default="hip", choices=("hip", "sdpa"))
 ap.add_argument("--kv-fp8", action="store_true",
                 help="fp8 KV caches (ops.Fp8KV) on the hip route")
@@ -38,14 +40,14 @@ args = ap.parse_args()
 # fp8 caches need the hip route; otherwise the defaults (TDPA_DECODE_ATTN)
 KV = {"attn_impl": "hip", "kv_dtype": "fp8"} if args.kv_fp8 else {}
 IMPL = KV.get("attn_impl")
-if args.int8:
+if args.int8 or args.int4:
     from torchdistpackage_amd.inference.generate import GraphedGPT2Decoder
-    from _decode_ab import int8_ab
+    from _decode_ab import weights_ab
     cfg.max_seq = 4096
     m = GPT2Model(cfg, device=dev, dtype=torch.bfloat16).eval()
-    int8_ab(m, GraphedGPT2Decoder, cfg.vocab_size, args.attn_impl,
-            "gpt2-1.3b")
-    print("DECODE BENCH INT8 AB OK")
+    weights_ab(m, GraphedGPT2Decoder, cfg.vocab_size, args.attn_impl,
+               "gpt2-1.3b", bits=(8, 4) if args.int4 else (8,))
+    print(f"DECODE BENCH INT{4 if args.int4 else 8} AB OK")
     sys.exit(0)
 m = GPT2Model(cfg, device=dev, dtype=torch.bfloat16).eval()
 idx = torch.randint(0, cfg.vocab_size, (B, PROMPT), device=dev)

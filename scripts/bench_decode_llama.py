@@ -3,6 +3,7 @@
 ``--int8`` runs the weight-only int8 A/B instead (scripts/_decode_ab.py):
 bf16 against ``quantize_linears_`` weights in the same process, B = 1 and 8
 at max_seq/prompt 192/128 and 4096/2048, ``--attn-impl`` in both arms.
+``--int4`` adds an int4 arm (``bits=4``): bf16, int8 and int4 in one process.
 
 ``--prefill-attn`` runs the prefill-attention A/B (scripts/
 kbench_prefill_attn.py): time to first token at a 2048-token prompt and
@@ -28,16 +29,18 @@ dev = torch.device("cuda")
 torch.manual_seed(0)
 ap = argparse.ArgumentParser()
 ap.add_argument("--int8", action="store_true")
+ap.add_argument("--int4", action="store_true")
 ap.add_argument("--prefill-attn", action="store_true")
 ap.add_argument("--kv-fp8", action="store_true")
 ap.add_argument("--attn-impl", default="hip", choices=("hip", "sdpa"))
 args = ap.parse_args()
 m = LlamaModel(llama3_8b(), device=dev, dtype=torch.bfloat16).eval()
 
-if args.int8:
-    from _decode_ab import int8_ab
-    int8_ab(m, GraphedLlamaDecoder, 128256, args.attn_impl, "llama-8b")
-    print("LLAMA DECODE INT8 AB OK")
+if args.int8 or args.int4:
+    from _decode_ab import weights_ab
+    weights_ab(m, GraphedLlamaDecoder, 128256, args.attn_impl, "llama-8b",
+               bits=(8, 4) if args.int4 else (8,))
+    print(f"LLAMA DECODE INT{4 if args.int4 else 8} AB OK")
     sys.exit(0)
 
 if args.prefill_attn:

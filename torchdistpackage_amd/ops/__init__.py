@@ -1143,6 +1143,8 @@ from .grouped import (GROUPED_GEMM_BM, grouped_gemm_eligible,  # noqa: E402
 
 from .int8 import (Int8Weight, int8_linear, quantize_int8,  # noqa: E402
                    quantize_linears_)
+from .int4 import (Int4Weight, int4_linear, is_int4_linear,  # noqa: E402
+                   pack_int4, quantize_int4, unpack_int4)
 
 # ---------------------------------------------------------------------------
 # fp8 (e4m3) KV cache: cache type, quantising append, dequantise; read by

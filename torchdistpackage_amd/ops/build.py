@@ -28,6 +28,7 @@ SOURCES = [
     "rope_swiglu.hip",
     "gemv.hip",
     "gemv_int8.hip",
+    "gemv_int4.hip",
     "decode_attn.hip",
     "decode_attn_fp8.hip",
     "kv_fp8.hip",

@@ -79,6 +79,9 @@ torch::Tensor gemv_bf16(torch::Tensor x, torch::Tensor W,
 torch::Tensor gemv_w8a16(torch::Tensor x, torch::Tensor q,
                          torch::Tensor scale,
                          c10::optional<torch::Tensor> bias);
+torch::Tensor gemv_w4a16(torch::Tensor x, torch::Tensor q,
+                         torch::Tensor scale,
+                         c10::optional<torch::Tensor> bias, int64_t arm);
 torch::Tensor rope_apply_pos(torch::Tensor x, torch::Tensor cs,
                              torch::Tensor sn, torch::Tensor pos, bool fwd);
 torch::Tensor decode_attention(torch::Tensor q, torch::Tensor k_cache,
@@ -169,6 +172,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ce_partial_fwd", &ce_partial_fwd);
   m.def("gemv_bf16", &gemv_bf16);
   m.def("gemv_w8a16", &gemv_w8a16);
+  m.def("gemv_w4a16", &gemv_w4a16,
+        "(x (M,K) bf16, q (N,K/2) uint8, scale (N,K/128) fp32, bias|None, "
+        "arm=0) -> (M,N) bf16, 1 <= M <= 32; arm 1 / 2 force the MFMA / dot2 "
+        "(M <= 4) arm",
+        pybind11::arg("x"), pybind11::arg("q"), pybind11::arg("scale"),
+        pybind11::arg("bias") = pybind11::none(), pybind11::arg("arm") = 0);
   m.def("rope_apply_pos", &rope_apply_pos);
   m.def("decode_attention", &decode_attention);
   m.def("prefill_attention", &prefill_attention,

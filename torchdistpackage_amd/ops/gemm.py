@@ -36,6 +36,7 @@ import torch.nn.functional as F
 
 from . import ext
 from .int8 import Int8Weight, int8_linear
+from .int4 import Int4Weight, int4_linear
 
 _MODE = os.environ.get("TDPA_GEMM", "1")
 _GEMV = os.environ.get("TDPA_GEMV", "1") == "1"
@@ -138,9 +139,12 @@ def linear(x: torch.Tensor, weight: torch.Tensor,
            bias: Optional[torch.Tensor] = None) -> torch.Tensor:
     """F.linear drop-in; routes 256-aligned bf16 GPU shapes through the
     per-GEMM measured dispatch (in-tree MFMA kernel vs hipBLASLt).  An
-    ``Int8Weight`` goes to ``int8_linear`` (ops/int8.py)."""
+    ``Int8Weight`` goes to ``int8_linear`` (ops/int8.py), an ``Int4Weight``
+    to ``int4_linear`` (ops/int4.py)."""
     if isinstance(weight, Int8Weight):
         return int8_linear(x, weight.q, weight.scale, bias)
+    if isinstance(weight, Int4Weight):
+        return int4_linear(x, weight.packed, weight.scale, bias)
     if (_MODE != "0" and x.is_cuda and x.dtype == torch.bfloat16
             and weight.dtype == torch.bfloat16
             and (bias is None or bias.dtype == torch.bfloat16)):

@@ -204,7 +204,8 @@ def is_int8_linear(module: nn.Module) -> bool:
     return getattr(type(module), "_tdpa_int8", False)
 
 
-def quantize_linears_(model: nn.Module, skip: Iterable[str] = ()) -> int:
+def quantize_linears_(model: nn.Module, skip: Iterable[str] = (),
+                      bits: int = 8) -> int:
     """Quantise every ``TpLinear`` / ``ColParallelLinear`` /
     ``RowParallelLinear`` / ``nn.Linear`` of ``model`` in place and return
     how many were converted.  The ``weight`` Parameter is dropped, int8
@@ -220,7 +221,15 @@ def quantize_linears_(model: nn.Module, skip: Iterable[str] = ()) -> int:
     The re-classed types are made at run time, so ``copy.deepcopy``,
     ``state_dict`` and ``load_state_dict`` (into an equally converted model)
     work, but pickling the whole module (``torch.save(model)``) does not:
-    save the state dict."""
+    save the state dict.
+
+    ``bits=4`` converts to the group-wise int4 format of ops/int4.py instead:
+    ``qweight`` is the packed uint8 (N, K/2), ``weight_scale`` is (N, K/128)
+    and ``module.weight`` an ``Int4Weight``.  A linear whose K is not a
+    multiple of 128 stays bf16 and is not counted."""
+    if bits not in (4, 8):
+        raise ValueError(f"quantize_linears_: bits must be 4 or 8, got {bits}")
+    from . import int4
     from ..parallel.tensor import get_tp_size
     assert get_tp_size() == 1, "quantize_linears_ supports tp=1 only"
     from ..moe.layer import Expert, ExpertParallelMoE, TopKRouter
@@ -236,12 +245,16 @@ def quantize_linears_(model: nn.Module, skip: Iterable[str] = ()) -> int:
                  if isinstance(m, moe_types)]
     count = 0
     for name, mod in list(model.named_modules()):
-        if not isinstance(mod, types) or is_int8_linear(mod):
+        if not isinstance(mod, types) or is_int8_linear(mod) \
+                or int4.is_int4_linear(mod):
             continue
         if under(name, skip) or under(name, moe_roots):
             continue
         w = mod._parameters.get("weight")
         if w is None or w.dim() != 2:
+            continue
+        if bits == 4:
+            count += int4.convert_linear_(mod)
             continue
         q, scale = quantize_int8(w)
         del mod._parameters["weight"]

@@ -62,3 +62,12 @@ def replace_linear_by_int8(model: nn.Module, skip=()) -> int:
     converted modules."""
     from ..ops import quantize_linears_
     return quantize_linears_(model, skip=skip)
+
+
+def replace_linear_by_int4(model: nn.Module, skip=()) -> int:
+    """Quantise the model's linears to weight-only int4 in place
+    (``ops.quantize_linears_(bits=4)``: scales per row and group of 128,
+    bf16 activations, the W4A16 MFMA kernel on the decode path).  Returns
+    the number of converted modules."""
+    from ..ops import quantize_linears_
+    return quantize_linears_(model, skip=skip, bits=4)
