@@ -11,7 +11,11 @@ ms/token of speculative decoding, ``TDPA_PREFILL_ATTN`` off against on.
 
 ``--kv-fp8`` runs the fp8 KV cache A/B (scripts/kbench_decode_attn_fp8.py):
 bf16 cache against fp8 cache on the hip route, ms/token, time to first token
-and resident cache bytes."""
+and resident cache bytes.
+
+``--kv-paged`` runs the paged KV cache A/B (scripts/
+kbench_decode_attn_paged.py): contiguous against paged caches (page 16,
+permuted table) on the hip route, ms/token at 4096/2048, B = 1 and 8."""
 import argparse
 import os
 import sys
@@ -32,6 +36,7 @@ ap.add_argument("--int8", action="store_true")
 ap.add_argument("--int4", action="store_true")
 ap.add_argument("--prefill-attn", action="store_true")
 ap.add_argument("--kv-fp8", action="store_true")
+ap.add_argument("--kv-paged", action="store_true")
 ap.add_argument("--attn-impl", default="hip", choices=("hip", "sdpa"))
 args = ap.parse_args()
 m = LlamaModel(llama3_8b(), device=dev, dtype=torch.bfloat16).eval()
@@ -53,6 +58,12 @@ if args.kv_fp8:
     from kbench_decode_attn_fp8 import end_to_end
     end_to_end(m)
     print("LLAMA KV FP8 AB OK")
+    sys.exit(0)
+
+if args.kv_paged:
+    from kbench_decode_attn_paged import end_to_end
+    end_to_end(m)
+    print("LLAMA KV PAGED AB OK")
     sys.exit(0)
 
 for B in (1, 8):

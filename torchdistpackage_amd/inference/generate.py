@@ -22,7 +22,7 @@ from typing import List, Optional, Tuple
 
 import torch
 
-from ..ops import Fp8KV, resolve_decode_attn_impl
+from ..ops import Fp8KV, PagedKV, resolve_decode_attn_impl
 from ..parallel.tensor import get_tp_size
 
 
@@ -38,15 +38,60 @@ def resolve_kv_dtype(kv_dtype: Optional[str] = None) -> str:
     return kv_dtype
 
 
+def resolve_kv_layout(kv_layout: Optional[str] = None,
+                      page_size: Optional[int] = None) -> Tuple[str, int]:
+    """``("contiguous" | "paged", page size)``.  ``"paged"`` keeps the
+    caches as ops.PagedKV (pools of ``page_size`` positions behind one block
+    table; needs ``attn_impl="hip"``).  ``None`` reads ``TDPA_KV_LAYOUT``
+    (default contiguous) and ``TDPA_KV_PAGE`` (default 16)."""
+    if kv_layout is None:
+        kv_layout = os.environ.get("TDPA_KV_LAYOUT", "contiguous")
+    if kv_layout not in ("contiguous", "paged"):
+        raise ValueError(f"kv_layout must be 'contiguous' or 'paged', got "
+                         f"{kv_layout!r}")
+    if page_size is None:
+        env = os.environ.get("TDPA_KV_PAGE", "16")
+        page_size = int(env) if env.isdigit() else env
+    # a contiguous cache has no pages: a stray value must not break it
+    if kv_layout == "paged" and page_size not in (16, 32, 64, 128):
+        raise ValueError("page_size must be a power of two in 16..128, got "
+                         f"{page_size!r}")
+    return kv_layout, page_size
+
+
 def _alloc_caches(model, batch: int, max_seq: int,
-                  kv_dtype: Optional[str] = None) -> List[Tuple]:
+                  kv_dtype: Optional[str] = None,
+                  kv_layout: Optional[str] = None,
+                  page_size: Optional[int] = None,
+                  block_table: Optional[torch.Tensor] = None) -> List[Tuple]:
     """Zeroed per-layer (k, v) caches (B, n_kv, max_seq, hd) for ``model``,
-    on its parameters' device: tensors of its dtype, or with
-    ``kv_dtype="fp8"`` pairs of ops.Fp8KV."""
+    on its parameters' device: tensors of its dtype, with ``kv_dtype="fp8"``
+    pairs of ops.Fp8KV, or with ``kv_layout="paged"`` pairs of ops.PagedKV.
+    A paged model has ONE block table (``block_table``, default the
+    identity), shared by every layer's K and V; each PagedKV has its own
+    pool."""
     cfg = model.cfg
     p = next(model.parameters())
     shape = (batch, getattr(cfg, "n_kv_head", cfg.n_head), max_seq,
              cfg.dim // cfg.n_head)
+    kv_layout, page_size = resolve_kv_layout(kv_layout, page_size)
+    if kv_layout == "paged":
+        if resolve_kv_dtype(kv_dtype) == "fp8":
+            raise ValueError("kv_layout='paged' with kv_dtype='fp8': there "
+                             "is no paged fp8 cache")
+        if block_table is not None and block_table.device != p.device:
+            raise ValueError(f"block_table on {block_table.device}, the "
+                             f"model on {p.device}")
+        first = PagedKV.zeros(*shape, page_size=page_size, dtype=p.dtype,
+                              device=p.device, block_table=block_table)
+        table = first.block_table
+
+        def one():
+            return PagedKV(torch.zeros_like(first.pool), table)
+        return [(first if i == 0 else one(), one())
+                for i in range(cfg.n_layer)]
+    if block_table is not None:
+        raise ValueError("block_table needs kv_layout='paged'")
     if resolve_kv_dtype(kv_dtype) == "fp8":
         return [(Fp8KV.zeros(*shape, device=p.device),
                  Fp8KV.zeros(*shape, device=p.device))
@@ -107,6 +152,11 @@ class GraphedDecoder:
     ``kv_dtype="fp8"`` (hip route only) keeps the caches as ops.Fp8KV; the
     quantising cache write is captured with the step.
 
+    ``kv_layout="paged"`` (hip route only) keeps them as ops.PagedKV behind
+    one block table (``self.caches[0][0].block_table``).  The captured step
+    reads the table's contents on the device, so the host may rewrite them in
+    place between replays.
+
     Greedy only (the argmax lives inside the graph).  Works for either
     model family (``GraphedGPT2Decoder`` and ``GraphedLlamaDecoder`` are
     this class); usage::
@@ -117,7 +167,9 @@ class GraphedDecoder:
 
     def __init__(self, model, batch: int, max_seq: int, warmup: int = 3,
                  attn_impl: Optional[str] = None,
-                 kv_dtype: Optional[str] = None):
+                 kv_dtype: Optional[str] = None,
+                 kv_layout: Optional[str] = None,
+                 page_size: Optional[int] = None):
         assert get_tp_size() == 1
         self.attn_impl = resolve_decode_attn_impl(attn_impl)
         assert torch.cuda.is_available()
@@ -126,7 +178,8 @@ class GraphedDecoder:
         p = next(model.parameters())
         dev, dtype = p.device, p.dtype
         self.max_seq = max_seq
-        self.caches = _alloc_caches(model, batch, max_seq, kv_dtype)
+        self.caches = _alloc_caches(model, batch, max_seq, kv_dtype,
+                                    kv_layout, page_size)
         self.in_tok = torch.zeros(batch, 1, dtype=torch.long, device=dev)
         self.pos_t = torch.zeros(1, dtype=torch.long, device=dev)
         self.pos = 0
@@ -203,7 +256,9 @@ def generate(model, idx: torch.Tensor, max_new_tokens: int,
              greedy: bool = True, temperature: float = 1.0,
              top_k: Optional[int] = None,
              attn_impl: Optional[str] = None,
-             kv_dtype: Optional[str] = None) -> torch.Tensor:
+             kv_dtype: Optional[str] = None,
+             kv_layout: Optional[str] = None,
+             page_size: Optional[int] = None) -> torch.Tensor:
     """Autoregressive generation with KV caches.
 
     Args:
@@ -215,13 +270,17 @@ def generate(model, idx: torch.Tensor, max_new_tokens: int,
         kv_dtype: KV cache format, ``"bf16"`` (the model's dtype) or
             ``"fp8"`` (needs ``attn_impl="hip"``); ``None`` reads
             ``TDPA_KV_DTYPE`` (default bf16).
+        kv_layout: ``"contiguous"`` or ``"paged"`` (ops.PagedKV caches of
+            ``page_size`` positions per page; needs ``attn_impl="hip"``);
+            ``None`` reads ``TDPA_KV_LAYOUT`` and ``TDPA_KV_PAGE`` (default
+            contiguous, 16).
     Returns (B, S0 + max_new_tokens) token ids.
     """
     assert get_tp_size() == 1, "generate() supports tp=1 (single device)"
     B, S0 = idx.shape
     total = S0 + max_new_tokens
     assert total <= model.cfg.max_seq, (total, model.cfg.max_seq)
-    caches = _alloc_caches(model, B, total, kv_dtype)
+    caches = _alloc_caches(model, B, total, kv_dtype, kv_layout, page_size)
 
     tokens = idx
     chunk, pos0 = idx, 0
@@ -239,7 +298,9 @@ def generate(model, idx: torch.Tensor, max_new_tokens: int,
 def speculative_generate(target, draft, idx: torch.Tensor,
                          max_new_tokens: int, k: int = 4,
                          attn_impl: Optional[str] = None,
-                         kv_dtype: Optional[str] = None) -> torch.Tensor:
+                         kv_dtype: Optional[str] = None,
+                         kv_layout: Optional[str] = None,
+                         page_size: Optional[int] = None) -> torch.Tensor:
     """Greedy speculative decoding: ``draft`` proposes ``k`` tokens per
     round, ``target`` verifies the whole chunk in ONE forward.  Output is
     EXACTLY the target's greedy generation — the draft only changes how
@@ -257,8 +318,8 @@ def speculative_generate(target, draft, idx: torch.Tensor,
     S0 = idx.shape[1]
     cap = S0 + max_new_tokens + k + 1
     assert cap <= target.cfg.max_seq and cap <= draft.cfg.max_seq
-    t_caches = _alloc_caches(target, 1, cap, kv_dtype)
-    d_caches = _alloc_caches(draft, 1, cap, kv_dtype)
+    t_caches = _alloc_caches(target, 1, cap, kv_dtype, kv_layout, page_size)
+    d_caches = _alloc_caches(draft, 1, cap, kv_dtype, kv_layout, page_size)
     attn_impl = resolve_decode_attn_impl(attn_impl)
     lt = decode_forward(target, idx, t_caches, 0, attn_impl=attn_impl)
     decode_forward(draft, idx, d_caches, 0, attn_impl=attn_impl)

@@ -65,6 +65,31 @@ def extension_available() -> bool:
     return _load_extension() is not None
 
 
+_EXT_NOPK = None
+
+
+def ext_nopk(required_for: str = "op"):
+    """The second in-tree module, ``_tdpa_nopk`` (ops/build.py: the
+    translation units built without packed-fp32 VALU forms); raises like
+    :func:`ext` when it is missing."""
+    global _EXT_NOPK
+    if _EXT_NOPK is None:
+        import glob
+        import importlib.util
+        here = os.path.dirname(os.path.abspath(__file__))
+        cands = glob.glob(os.path.join(here, "_tdpa_nopk*.so"))
+        if not cands:
+            raise RuntimeError(
+                f"HIP extension required for {required_for} on GPU but "
+                f"_tdpa_nopk not found under {here}; run `python -m "
+                "torchdistpackage_amd.ops.build` (or __graft_entry__.build())")
+        spec = importlib.util.spec_from_file_location("_tdpa_nopk", cands[0])
+        mod = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(mod)
+        _EXT_NOPK = mod
+    return _EXT_NOPK
+
+
 # ---------------------------------------------------------------------------
 # RMSNorm
 # ---------------------------------------------------------------------------
@@ -819,6 +844,12 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor,
     row, written by :func:`kv_cache_append`): the GPU runs the fp8 variant
     of the kernel under the same contract, the CPU dequantises (exactly)
     and runs the oracle.  One Fp8KV and one tensor raise.
+
+    Or a pair of :class:`PagedKV` (a pool of pages and a block table that
+    both share): the GPU runs the paged variant of the bf16 kernel
+    (csrc/decode_attn_paged.hip), bit-equal to the contiguous kernel on the
+    same values at the same chunk length; the CPU gathers and runs the
+    oracle.  One PagedKV and one tensor raise.
     """
     B, Hq, Sq, D = q.shape
     Hkv = k_cache.shape[1]
@@ -831,6 +862,11 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor,
     if fp8 != isinstance(v_cache, Fp8KV):
         raise TypeError("decode_attention: k_cache and v_cache must both be "
                         "Fp8KV or both be tensors")
+    paged = isinstance(k_cache, PagedKV) or isinstance(v_cache, PagedKV)
+    if paged:
+        paged_kv._check_pair(k_cache, v_cache, "decode_attention")
+        if not q.is_cuda:
+            k_cache, v_cache = k_cache.gather(), v_cache.gather()
     if fp8 and not q.is_cuda:
         # the oracle attends to the dequantised values, exact in fp32
         k_cache = k_cache.dequantize(torch.float32)
@@ -859,6 +895,17 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor,
             e.decode_attention_fp8(q_, k_cache.data, k_cache.scale,
                                    v_cache.data, v_cache.scale, o_, pos_t,
                                    p0, float(scale), skv)
+    elif paged:
+        if k_cache.pool.dtype != torch.bfloat16:
+            raise TypeError("decode_attention: the GPU kernel reads bf16 "
+                            f"pools, got {k_cache.pool.dtype}")
+
+        ep = ext_nopk("decode_attention")
+
+        def launch(q_, o_, pos_t, p0):
+            ep.decode_attention_paged(q_, k_cache.pool, v_cache.pool,
+                                     k_cache.block_table, o_, pos_t, p0,
+                                     float(scale), skv)
     else:
         def launch(q_, o_, pos_t, p0):
             e.decode_attention(q_, k_cache, v_cache, o_, pos_t, p0,
@@ -1151,4 +1198,6 @@ from .int4 import (Int4Weight, int4_linear, is_int4_linear,  # noqa: E402
 # decode_attention above
 # ---------------------------------------------------------------------------
 
-from .kv_fp8 import Fp8KV, kv_cache_append, quantize_kv_rows  # noqa: E402
+from . import paged_kv  # noqa: E402
+from .kv_fp8 import Fp8KV, quantize_kv_rows  # noqa: E402
+from .paged_kv import PagedKV, kv_cache_append  # noqa: E402

@@ -36,19 +36,29 @@ SOURCES = [
     "grouped_gemm.hip",
 ]
 
+# A second module, ``_tdpa_nopk``: translation units built without
+# packed-fp32 VALU forms.  It is a compiler flag for the whole unit (headers
+# and device library included), which one module's sources cannot take one by
+# one; a function attribute instead stops every header inline from inlining
+# into the kernels (docs/design/kernels.md, "decode_attn_paged.hip").
+NOPK_SOURCES = [
+    "bindings_nopk.cpp",
+    "decode_attn_paged.hip",
+]
+NOPK_FLAGS = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 
-def build(verbose: bool = True) -> str:
-    os.environ.setdefault("PYTORCH_ROCM_ARCH", "gfx950")
-    os.environ.setdefault("MAX_JOBS", str(min(os.cpu_count() or 4, 16)))
+
+def _build_module(name: str, sources, hip_flags, verbose: bool) -> str:
     from torch.utils.cpp_extension import load
 
-    build_dir = os.path.join(HERE, "_build")
+    build_dir = os.path.join(HERE, "_build", name) if name != "_tdpa_hip" \
+        else os.path.join(HERE, "_build")
     os.makedirs(build_dir, exist_ok=True)
-    mod = load(
-        name="_tdpa_hip",
-        sources=[os.path.join(CSRC, s) for s in SOURCES],
+    load(
+        name=name,
+        sources=[os.path.join(CSRC, s) for s in sources],
         extra_cflags=["-O3"],
-        extra_cuda_cflags=["-O3", "--offload-arch=gfx950"],
+        extra_cuda_cflags=["-O3", "--offload-arch=gfx950"] + hip_flags,
         build_directory=build_dir,
         verbose=verbose,
         is_python_module=False,  # just build; we load it ourselves
@@ -56,12 +66,20 @@ def build(verbose: bool = True) -> str:
     # copy the built .so next to this file (in-tree, snapshot-visible)
     import glob
     import shutil
-    sos = glob.glob(os.path.join(build_dir, "_tdpa_hip*.so"))
+    sos = glob.glob(os.path.join(build_dir, name + "*.so"))
     assert sos, f"no .so produced in {build_dir}"
     dest = os.path.join(HERE, os.path.basename(sos[0]))
     shutil.copy2(sos[0], dest)
     if verbose:
         print(f"[ops.build] built {dest}")
+    return dest
+
+
+def build(verbose: bool = True) -> str:
+    os.environ.setdefault("PYTORCH_ROCM_ARCH", "gfx950")
+    os.environ.setdefault("MAX_JOBS", str(min(os.cpu_count() or 4, 16)))
+    dest = _build_module("_tdpa_hip", SOURCES, [], verbose)
+    _build_module("_tdpa_nopk", NOPK_SOURCES, NOPK_FLAGS, verbose)
     return dest
 
 

@@ -1,7 +1,9 @@
 // What the split-KV decode-attention kernels share (decode_attn.hip over a
-// bf16 cache, decode_attn_fp8.hip over an fp8 cache): the DPP lane-group
-// reduction, the clamped position read, the split choice and the body of the
-// combine launch.
+// bf16 cache, decode_attn_paged.hip over a paged bf16 cache,
+// decode_attn_fp8.hip over an fp8 cache): the DPP lane-group reduction, the
+// clamped position read, the split choice and the body of the combine
+// launch.  The body of the first launch of the two bf16 kernels is shared as
+// text, in decode_attn_body.inc.
 #pragma once
 
 #include <algorithm>
@@ -11,6 +13,7 @@
 #define DA_BLOCK 256
 #define DA_WAVES (DA_BLOCK / WAVE)
 #define DA_MAX_M 16
+#define DA_MAX_IDS 4096   // page ids a paged workgroup keeps in LDS (16 KB)
 
 typedef short da_sv2 __attribute__((ext_vector_type(2)));
 
@@ -86,4 +89,13 @@ static inline int da_choose_chunk(int Smax, int BH, long split_kv, int cus) {
     return (int)std::min<long>((split_kv + 63) / 64 * 64, 1L << 30);
   const int want = std::max(1, (2 * cus + BH - 1) / BH);
   return ((Smax + want - 1) / want + 63) / 64 * 64;
+}
+
+// The same for a paged cache: a whole number of pages, a multiple of
+// max(64, page), and at most DA_MAX_IDS pages (then nsplit grows instead)
+static inline int da_choose_chunk_paged(int Smax, int BH, long split_kv,
+                                        int cus, int page) {
+  const long m = std::max(64, page);
+  const long c = da_choose_chunk(Smax, BH, split_kv, cus);
+  return (int)std::min<long>((c + m - 1) / m * m, (long)DA_MAX_IDS * page);
 }

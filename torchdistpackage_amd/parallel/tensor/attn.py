@@ -82,6 +82,9 @@ def _cached_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     ops.kv_cache_append (one quantising launch for K and V, either ``pos0``
     form), decode_attention runs its fp8 kernel, and a chunk that goes to
     prefill_attention reads a transient bf16 copy of the visible prefix.
+    A pair of ops.PagedKV takes the same branches: kv_cache_append writes
+    through the block table, decode_attention runs its paged kernel, and the
+    prefill route reads ``gather(pos0 + S)`` as a transient dense copy.
     """
     B, H, S, hd = q.shape
     hip = resolve_decode_attn_impl(attn_impl) == "hip"
@@ -91,6 +94,12 @@ def _cached_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
         raise ValueError("fp8 KV caches need attn_impl='hip' "
                          "(ops.decode_attention reads them); attn_impl="
                          "'sdpa' has no fp8 path")
+    paged = isinstance(k_cache, ops.PagedKV) or \
+        isinstance(v_cache, ops.PagedKV)
+    if paged and not hip:
+        raise ValueError("paged KV caches need attn_impl='hip' "
+                         "(ops.decode_attention reads them); attn_impl="
+                         "'sdpa' has no paged path")
     if on_device:
         if S != 1:
             raise ValueError(f"tensor pos0 is the single-token step, got "
@@ -98,7 +107,7 @@ def _cached_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
         if not hip and mask is None:
             raise ValueError("tensor pos0 with attn_impl='sdpa' needs the "
                              "cache visibility mask")
-    if fp8:
+    if fp8 or paged:
         ops.kv_cache_append(k_cache, v_cache, k, v, pos0)
     elif on_device:
         k_cache.index_copy_(2, pos0, k)
@@ -118,6 +127,10 @@ def _cached_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
                 # decode kernel attends to)
                 k_cache = k_cache.dequantize(torch.bfloat16, pos0 + S)
                 v_cache = v_cache.dequantize(torch.bfloat16, pos0 + S)
+            elif paged:
+                # no paged arm in the prefill kernel either
+                k_cache = k_cache.gather(pos0 + S)
+                v_cache = v_cache.gather(pos0 + S)
             o = ops.prefill_attention(q, k_cache, v_cache, pos0)
         else:
             o = ops.decode_attention(q, k_cache, v_cache, pos0)
