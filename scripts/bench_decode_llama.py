@@ -9,6 +9,10 @@ at max_seq/prompt 192/128 and 4096/2048, ``--attn-impl`` in both arms.
 kbench_prefill_attn.py): time to first token at a 2048-token prompt and
 ms/token of speculative decoding, ``TDPA_PREFILL_ATTN`` off against on.
 
+``--chunk-attn`` runs the chunk-attention A/B (scripts/kbench_chunk_attn.py):
+ms/token of speculative decoding with k = 8 at context 2048,
+``TDPA_CHUNK_ATTN`` off against on.
+
 ``--kv-fp8`` runs the fp8 KV cache A/B (scripts/kbench_decode_attn_fp8.py):
 bf16 cache against fp8 cache on the hip route, ms/token, time to first token
 and resident cache bytes.
@@ -35,6 +39,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--int8", action="store_true")
 ap.add_argument("--int4", action="store_true")
 ap.add_argument("--prefill-attn", action="store_true")
+ap.add_argument("--chunk-attn", action="store_true")
 ap.add_argument("--kv-fp8", action="store_true")
 ap.add_argument("--kv-paged", action="store_true")
 ap.add_argument("--attn-impl", default="hip", choices=("hip", "sdpa"))
@@ -52,6 +57,12 @@ if args.prefill_attn:
     from kbench_prefill_attn import end_to_end
     end_to_end(m)
     print("LLAMA PREFILL ATTN AB OK")
+    sys.exit(0)
+
+if args.chunk_attn:
+    from kbench_chunk_attn import end_to_end
+    end_to_end(m)
+    print("LLAMA CHUNK ATTN AB OK")
     sys.exit(0)
 
 if args.kv_fp8:

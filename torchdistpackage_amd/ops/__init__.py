@@ -1012,6 +1012,93 @@ def prefill_attention(q: torch.Tensor, k_cache: torch.Tensor,
     return o4
 
 
+# ---------------------------------------------------------------------------
+# chunk attention over a KV cache (split-KV MFMA kernel): the same contract
+# for 1..64 query rows per kv head in one split-KV launch pair
+# ---------------------------------------------------------------------------
+
+# TDPA_CHUNK_ATTN=1 lets the hip cached-attention route send host-int chunks
+# of 17.._CHUNK_MAX_ROWS rows per kv head to chunk_attention (read once, here)
+_CHUNK_ATTN = os.environ.get("TDPA_CHUNK_ATTN", "0") == "1"
+
+_CHUNK_KERNEL_ROWS = 64   # query rows per kv head the kernel serves
+
+
+def chunk_attention_enabled() -> bool:
+    return _CHUNK_ATTN
+
+
+def set_chunk_attention(on: bool) -> bool:
+    """Switch the chunk-attention routing of the hip cached-attention route
+    on or off for this process; returns the previous setting.  For tests
+    and same-process A/B runs."""
+    global _CHUNK_ATTN
+    prev, _CHUNK_ATTN = _CHUNK_ATTN, bool(on)
+    return prev
+
+
+def chunk_attention(q: torch.Tensor, k_cache: torch.Tensor,
+                    v_cache: torch.Tensor, pos0, scale: float = None,
+                    split_kv: Optional[int] = None) -> torch.Tensor:
+    """Causal attention of a short chunk of new query rows against a KV
+    cache: up to 64 rows per kv head (``(Hq/Hkv) * Sq <= 64``), split over
+    the keys like :func:`decode_attention` and on MFMA like
+    :func:`prefill_attention` (speculative verification, small
+    chunked-prefill steps).
+
+    Shapes, ``pos0`` forms (host int, or int64 tensor of 1 or B elements
+    read on the device), errors and the returned layout are those of
+    :func:`decode_attention`.  A tensor ``pos0`` works at any admissible
+    ``Sq``, so a multi-row step wider than 16 rows captures into a hipGraph.
+
+    GPU bf16 runs the HIP kernel (csrc/chunk_attn.hip; head dim 64 or 128,
+    dense bf16 caches; anything else raises — there is no composite path).
+    CPU tensors of any float dtype run exact fp32 math (the oracle).
+    ``split_kv`` overrides the KV chunk length per workgroup (tests).
+    """
+    if isinstance(k_cache, (Fp8KV, PagedKV)) or \
+            isinstance(v_cache, (Fp8KV, PagedKV)):
+        raise TypeError("chunk_attention: the kernel reads dense bf16 caches; "
+                        "Fp8KV and PagedKV go to decode_attention")
+    B, Hq, Sq, D = q.shape
+    Hkv = k_cache.shape[1]
+    if Hq % Hkv != 0:
+        raise ValueError(f"chunk_attention: Hq={Hq} not a multiple of "
+                         f"Hkv={Hkv}")
+    if (Hq // Hkv) * Sq > _CHUNK_KERNEL_ROWS:
+        raise ValueError(f"chunk_attention: (Hq/Hkv)*Sq={(Hq // Hkv) * Sq} "
+                         f"exceeds {_CHUNK_KERNEL_ROWS} rows per kv head; "
+                         "use prefill_attention for longer chunks")
+    if scale is None:
+        scale = 1.0 / math.sqrt(D)
+    if not q.is_cuda:
+        o = _decode_attention_ref(q, k_cache, v_cache, pos0, scale)
+        o_buf = o.permute(2, 0, 1, 3).contiguous()      # (Sq, B, Hq, D)
+        return o_buf.permute(1, 2, 0, 3)
+    if q.dtype != torch.bfloat16:
+        raise TypeError("chunk_attention: the GPU kernel is bf16-only, got "
+                        f"{q.dtype}")
+    if D not in (64, 128):
+        raise ValueError("chunk_attention: the GPU kernel covers head dim "
+                         f"64 and 128, got {D}")
+    if Sq < 1 or Sq > k_cache.shape[2]:
+        raise ValueError(f"chunk_attention: Sq={Sq} outside the cache "
+                         f"(Smax={k_cache.shape[2]})")
+    e = ext("chunk_attention")
+    o_buf = torch.empty(Sq, B, Hq * D, dtype=q.dtype, device=q.device)
+    o4 = o_buf.view(Sq, B, Hq, D).permute(1, 2, 0, 3)
+    skv = int(split_kv or 0)
+    if torch.is_tensor(pos0):
+        e.chunk_attention(q, k_cache, v_cache, o4, pos0, 0, float(scale), skv)
+        return o4
+    pos0 = int(pos0)
+    if pos0 < 0 or pos0 + Sq > k_cache.shape[2]:
+        raise ValueError(f"chunk_attention: pos0={pos0} with Sq={Sq} "
+                         f"outside the cache (Smax={k_cache.shape[2]})")
+    e.chunk_attention(q, k_cache, v_cache, o4, None, pos0, float(scale), skv)
+    return o4
+
+
 class _CrossEntropyFn(torch.autograd.Function):
     """Fused mean cross-entropy on bf16 logits (one online-LSE pass fwd, one
     dlogits pass bwd) — replaces logits.float()+F.cross_entropy which

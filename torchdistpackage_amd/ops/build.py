@@ -33,6 +33,7 @@ SOURCES = [
     "decode_attn_fp8.hip",
     "kv_fp8.hip",
     "prefill_attn.hip",
+    "chunk_attn.hip",
     "grouped_gemm.hip",
 ]
 

@@ -92,6 +92,10 @@ torch::Tensor prefill_attention(torch::Tensor q, torch::Tensor k_cache,
                                 torch::Tensor v_cache, torch::Tensor out,
                                 c10::optional<torch::Tensor> pos_t, long pos0,
                                 double scale, long pos_tile);
+torch::Tensor chunk_attention(torch::Tensor q, torch::Tensor k_cache,
+                              torch::Tensor v_cache, torch::Tensor out,
+                              c10::optional<torch::Tensor> pos_t, long pos0,
+                              double scale, long split_kv);
 torch::Tensor decode_attention_fp8(torch::Tensor q, torch::Tensor k_data,
                                    torch::Tensor k_scale,
                                    torch::Tensor v_data,
@@ -182,6 +186,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("decode_attention", &decode_attention);
   m.def("prefill_attention", &prefill_attention,
         "(q, k_cache, v_cache, out, pos_t|None, pos0, scale, pos_tile) -> out");
+  m.def("chunk_attention", &chunk_attention,
+        "(q, k_cache, v_cache, out, pos_t|None, pos0, scale, split_kv) -> out");
   m.def("decode_attention_fp8", &decode_attention_fp8,
         "(q, k_data, k_scale, v_data, v_scale, out, pos_t|None, pos0, scale, "
         "split_kv) -> out");

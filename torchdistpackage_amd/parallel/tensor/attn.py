@@ -52,6 +52,13 @@ def _cached_sdpa(q: torch.Tensor, k_cache: torch.Tensor,
 # inference.md "Prefill attention" has the table).
 _PREFILL_MIN_ROWS = 64
 
+# Rows per kv head (G * S) up to which the hip route, with TDPA_CHUNK_ATTN on,
+# sends a host-int-pos0 chunk of more than one decode_attention launch (16
+# rows) to ops.chunk_attention, the split-KV MFMA kernel.  64 is what the
+# kernel serves (docs/design/inference.md "Chunk attention" has the table).
+_CHUNK_MIN_ROWS = 16
+_CHUNK_MAX_ROWS = 64
+
 
 def _cached_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
                       k_cache: torch.Tensor, v_cache: torch.Tensor, pos0,
@@ -76,7 +83,10 @@ def _cached_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     with either form; the SDPA routes expand K/V heads to Q heads first.
     With ``TDPA_PREFILL_ATTN`` on, a host-int chunk of more than
     ``_PREFILL_MIN_ROWS`` rows per kv head runs ops.prefill_attention instead
-    (one launch, where decode_attention would loop on the host).
+    (one launch, where decode_attention would loop on the host).  With
+    ``TDPA_CHUNK_ATTN`` on, a host-int chunk of more than ``_CHUNK_MIN_ROWS``
+    and at most ``_CHUNK_MAX_ROWS`` rows per kv head over dense bf16 caches
+    runs ops.chunk_attention; that branch is checked first.
 
     The caches may be a pair of ops.Fp8KV (hip route only): the write is
     ops.kv_cache_append (one quantising launch for K and V, either ``pos0``
@@ -119,8 +129,12 @@ def _cached_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
         assert causal or S == 1, \
             "decode_attention is causal over the new rows"
         G = H // k_cache.shape[1]
-        if (not on_device and ops.prefill_attention_enabled()
-                and G * S > _PREFILL_MIN_ROWS):
+        if (not on_device and not fp8 and not paged
+                and ops.chunk_attention_enabled()
+                and _CHUNK_MIN_ROWS < G * S <= _CHUNK_MAX_ROWS):
+            o = ops.chunk_attention(q, k_cache, v_cache, pos0)
+        elif (not on_device and ops.prefill_attention_enabled()
+              and G * S > _PREFILL_MIN_ROWS):
             if fp8:
                 # no fp8 arm in the prefill kernel: it reads a transient
                 # bf16 copy of the visible prefix (the same values the fp8
