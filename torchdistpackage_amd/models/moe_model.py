@@ -25,6 +25,7 @@ from .gpt2 import GPT2Config, GPT2Embedding, GPT2Head
 
 
 EXPERT_IMPLS = ("loop", "batched", "grouped")
+ROUTE_IMPLS = ("torch", "fused")
 
 
 @dataclass
@@ -45,8 +46,16 @@ class MoEConfig:
     # HIP GEMM).  Default from TDPA_MOE_EXPERTS (docs/knobs.md).
     expert_impl: str = field(
         default_factory=lambda: os.environ.get("TDPA_MOE_EXPERTS", "loop"))
+    # token routing around the experts: "torch" (argsort / gather /
+    # index_add_) or "fused" (the counting-sort plan and the dispatch and
+    # combine HIP kernels).  Default from TDPA_MOE_ROUTE (docs/knobs.md).
+    route_impl: str = field(
+        default_factory=lambda: os.environ.get("TDPA_MOE_ROUTE", "torch"))
 
     def __post_init__(self):
+        if self.route_impl not in ROUTE_IMPLS:
+            raise ValueError(f"route_impl must be one of {ROUTE_IMPLS}, "
+                             f"got {self.route_impl!r}")
         if self.expert_impl not in EXPERT_IMPLS:
             raise ValueError(f"expert_impl must be one of {EXPERT_IMPLS}, "
                              f"got {self.expert_impl!r}")
@@ -76,6 +85,7 @@ class MoEBlock(nn.Module):
                                      cfg.hidden_mult,
                                      batched=cfg.expert_impl == "batched",
                                      grouped=cfg.expert_impl == "grouped",
+                                     route=cfg.route_impl,
                                      **kw)
 
     def forward(self, x):

@@ -32,6 +32,8 @@ import torch.nn.functional as F
 
 from ..ops import bias_gelu
 
+ROUTE_IMPLS = ("torch", "fused")
+
 
 def mark_expert_parallel(module: nn.Module):
     for p in module.parameters():
@@ -271,11 +273,18 @@ class ExpertParallelMoE(nn.Module):
                  ep_group: Optional[dist.ProcessGroup] = None,
                  batched: bool = False,
                  grouped: bool = False,
+                 route: str = "torch",
                  device=None, dtype=None):
         super().__init__()
         if batched and grouped:
             raise ValueError("ExpertParallelMoE: batched and grouped are "
                              "exclusive")
+        if route not in ROUTE_IMPLS:
+            raise ValueError(f"ExpertParallelMoE: route must be one of "
+                             f"{ROUTE_IMPLS}, got {route!r}")
+        # "fused": ops.moe_route_plan / moe_dispatch / moe_combine replace
+        # the argsort / gather / index_add_ chain around the experts
+        self.route = route
         if ep_group is None:
             try:
                 from ..dist.topo import tpc
@@ -320,13 +329,22 @@ class ExpertParallelMoE(nn.Module):
         topk_idx, topk_gate, aux = self.router(xt)
         self.aux_loss = aux
 
-        # one routing entry per (token, k): expert id + flat token id
-        flat_expert = topk_idx.reshape(-1)                       # (N*k,)
-        order = torch.argsort(flat_expert, stable=True)          # sort by expert
-        token_of = order // self.top_k                           # src token
-        sorted_expert = flat_expert[order]
+        fused = self.route == "fused"
+        if fused:
+            from ..ops import moe_combine, moe_dispatch, moe_route_plan
+            # dest[t, j]: row of entry (t, j) in the expert-sorted buffer,
+            # the inverse of the stable argsort below, so the split lists
+            # slice the same rows on both routes
+            dest, counts, offs_all = moe_route_plan(topk_idx,
+                                                    self.num_experts)
+        else:
+            # one routing entry per (token, k): expert id + flat token id
+            flat_expert = topk_idx.reshape(-1)                   # (N*k,)
+            order = torch.argsort(flat_expert, stable=True)      # sort by expert
+            token_of = order // self.top_k                       # src token
+            sorted_expert = flat_expert[order]
 
-        counts = torch.bincount(flat_expert, minlength=self.num_experts)
+            counts = torch.bincount(flat_expert, minlength=self.num_experts)
         # exchange counts so we know how much we receive per rank.  Device
         # tensor all-gather (one RCCL call riding xGMI) + ONE host sync for
         # the split lists — all_to_all_single's split args must be Python
@@ -353,7 +371,8 @@ class ExpertParallelMoE(nn.Module):
             in_splits = [int(my_slice_host.sum())]
             out_splits = in_splits
 
-        dispatched = xt[token_of]                                # (N*k, D)
+        dispatched = moe_dispatch(xt, dest) if fused \
+            else xt[token_of]                                    # (N*k, D)
         if self.ep_size > 1:
             received = _AllToAll.apply(dispatched, in_splits, out_splits,
                                        self.ep_group)
@@ -366,13 +385,25 @@ class ExpertParallelMoE(nn.Module):
         # MoE bench step)
         # all index bookkeeping on DEVICE: cpu repeat_interleave measured
         # ~5.5 ms per call on this host (264 ms per 24-layer forward)
-        seg_sizes_dev = my_slice.reshape(-1).to(received.device)
-        seg_expert_dev = torch.arange(
-            self.ep_size * self.num_local,
-            device=received.device) % self.num_local
-        tok_expert = torch.repeat_interleave(seg_expert_dev, seg_sizes_dev)
-        order2 = torch.argsort(tok_expert, stable=True)
-        grouped = received[order2]
+        offs = None
+        if fused and self.ep_size == 1:
+            # already sorted by (local = global) expert: no regroup
+            grouped, offs = received, offs_all
+        else:
+            seg_sizes_dev = my_slice.reshape(-1).to(received.device)
+            seg_expert_dev = torch.arange(
+                self.ep_size * self.num_local,
+                device=received.device) % self.num_local
+            tok_expert = torch.repeat_interleave(seg_expert_dev,
+                                                 seg_sizes_dev)
+            if fused:
+                # the same ops at k = 1 regroup the received rows
+                dest2, _, offs = moe_route_plan(tok_expert[:, None],
+                                                self.num_local)
+                grouped = moe_dispatch(received, dest2)
+            else:
+                order2 = torch.argsort(tok_expert, stable=True)
+                grouped = received[order2]
         per_expert = my_slice_host.sum(0).tolist()  # host table, no extra sync
         # Quantize each expert's batch to a multiple of 1024 (zero-padded,
         # padding sliced off the output).  Routing drifts every step, and
@@ -382,8 +413,9 @@ class ExpertParallelMoE(nn.Module):
         if self.grouped:
             # segment table built on the device; nothing below reads it on
             # the host
-            cnt_dev = my_slice.sum(0).to(received.device)
-            offs = F.pad(torch.cumsum(cnt_dev, 0), (1, 0))
+            if offs is None:
+                cnt_dev = my_slice.sum(0).to(received.device)
+                offs = F.pad(torch.cumsum(cnt_dev, 0), (1, 0))
             y_all = self.experts_g(grouped, offs)
         elif self.batched:
             cnt_dev = my_slice.sum(0).to(received.device)
@@ -405,8 +437,12 @@ class ExpertParallelMoE(nn.Module):
                     y_parts.append(self.experts[le](seg)[:n])
                 off += n
             y_all = torch.cat(y_parts, dim=0) if y_parts else grouped[:0]
-        outs = torch.empty_like(received)
-        outs[order2] = y_all
+        if fused:
+            outs = y_all if self.ep_size == 1 \
+                else moe_combine(y_all, dest2, None)
+        else:
+            outs = torch.empty_like(received)
+            outs[order2] = y_all
 
         # mirror the dispatch guard: with ep_size==1 _AllToAll would see the
         # WORLD size of group=None and issue a bogus all_to_all
@@ -416,6 +452,9 @@ class ExpertParallelMoE(nn.Module):
         else:
             returned = outs
 
+        if fused:
+            # gates stay fp32; fp32 accumulation over k, one rounding
+            return moe_combine(returned, dest, topk_gate).reshape(orig_shape)
         # un-sort and combine with gates
         gates = topk_gate.reshape(-1)[order].to(returned.dtype)  # (N*k,)
         combined = torch.zeros_like(xt)

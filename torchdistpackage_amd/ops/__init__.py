@@ -1272,6 +1272,13 @@ from .grouped import (GROUPED_GEMM_BM, grouped_gemm_eligible,  # noqa: E402
                       grouped_linear)
 
 # ---------------------------------------------------------------------------
+# fused MoE token routing: counting-sort plan, dispatch, combine
+# ---------------------------------------------------------------------------
+
+from .moe_route import (MOE_PLAN_CHUNK, moe_combine, moe_dispatch,  # noqa: E402
+                        moe_route_eligible, moe_route_plan)
+
+# ---------------------------------------------------------------------------
 # weight-only int8 linear for decode (W8A16 GEMV kernel)
 # ---------------------------------------------------------------------------
 

@@ -35,6 +35,7 @@ SOURCES = [
     "prefill_attn.hip",
     "chunk_attn.hip",
     "grouped_gemm.hip",
+    "moe_route.hip",
 ]
 
 # A second module, ``_tdpa_nopk``: translation units built without

@@ -2,6 +2,7 @@
 #include <torch/extension.h>
 
 #include "grouped_gemm_plan.h"
+#include "moe_route.h"
 
 std::vector<torch::Tensor> rmsnorm_fwd(torch::Tensor x, torch::Tensor w,
                                        double eps);
@@ -117,6 +118,13 @@ std::tuple<torch::Tensor, c10::optional<torch::Tensor>> grouped_gemm_wgrad(
     torch::Tensor dy, torch::Tensor x, torch::Tensor offs,
     bool want_bias_grad);
 torch::Tensor grouped_gemm_plan(torch::Tensor offs_cpu, int64_t T);
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> moe_route_plan(
+    torch::Tensor topk_idx, int64_t num_experts);
+torch::Tensor moe_route_gather(torch::Tensor y, torch::Tensor dest,
+                               c10::optional<torch::Tensor> gates);
+std::tuple<torch::Tensor, c10::optional<torch::Tensor>> moe_route_scatter(
+    torch::Tensor x, torch::Tensor dest, c10::optional<torch::Tensor> gates,
+    c10::optional<torch::Tensor> y);
 std::vector<torch::Tensor> bias_residual_layernorm_fwd(
     torch::Tensor y, c10::optional<torch::Tensor> bias, torch::Tensor x_res,
     torch::Tensor ln_w, torch::Tensor ln_b, double eps);
@@ -202,6 +210,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "(offs_cpu, T) -> (row-tile bound, 3) int64: (expert, first row, "
         "row count) per block, expert -1 = idle");
   m.attr("GROUPED_GEMM_BM") = GG_BM;
+  m.def("moe_route_plan", &moe_route_plan,
+        "(topk_idx (N,k) int32|int64, num_experts) -> (dest (N,k) int32, "
+        "counts (E,) int64, offs (E+1,) int64)");
+  m.def("moe_route_gather", &moe_route_gather,
+        "(y (N*k,D), dest, gates|None) -> (N,D): sum_j gates * y[dest]");
+  m.def("moe_route_scatter", &moe_route_scatter,
+        "(x (N,D), dest, gates|None, y|None) -> (out (N*k,D), dgates|None): "
+        "out[dest] = gates * x, dgates = x . y[dest]");
+  m.attr("MOE_PLAN_CHUNK") = MOE_PLAN_CHUNK;
   m.def("bias_residual_layernorm_fwd", &bias_residual_layernorm_fwd,
         "(y, bias|None, x_res, ln_w, ln_b, eps) -> (x_new, h, mean, rstd)");
   m.def("layernorm_bwd_residual", &layernorm_bwd_residual,
