@@ -19,7 +19,12 @@ and resident cache bytes.
 
 ``--kv-paged`` runs the paged KV cache A/B (scripts/
 kbench_decode_attn_paged.py): contiguous against paged caches (page 16,
-permuted table) on the hip route, ms/token at 4096/2048, B = 1 and 8."""
+permuted table) on the hip route, ms/token at 4096/2048, B = 1 and 8.
+
+``--sample`` runs the sampling A/B (scripts/kbench_sample.py): graphed greedy
+against graphed sampled decode (ops.sample_logits inside the graph) and eager
+``generate`` with ``sampler="torch"`` against ``"hip"``, ms/token at
+4096/2048, B = 1 and 8."""
 import argparse
 import os
 import sys
@@ -42,6 +47,7 @@ ap.add_argument("--prefill-attn", action="store_true")
 ap.add_argument("--chunk-attn", action="store_true")
 ap.add_argument("--kv-fp8", action="store_true")
 ap.add_argument("--kv-paged", action="store_true")
+ap.add_argument("--sample", action="store_true")
 ap.add_argument("--attn-impl", default="hip", choices=("hip", "sdpa"))
 args = ap.parse_args()
 m = LlamaModel(llama3_8b(), device=dev, dtype=torch.bfloat16).eval()
@@ -75,6 +81,12 @@ if args.kv_paged:
     from kbench_decode_attn_paged import end_to_end
     end_to_end(m)
     print("LLAMA KV PAGED AB OK")
+    sys.exit(0)
+
+if args.sample:
+    from kbench_sample import end_to_end
+    end_to_end(m)
+    print("LLAMA SAMPLE AB OK")
     sys.exit(0)
 
 for B in (1, 8):

@@ -3,7 +3,8 @@
 The reference has no inference path at all (its ``forward_eval`` pipelines
 full forwards, pipeline_sched.py:233-269); this module adds the serving-side
 basics: prefill + incremental decode with per-layer K/V caches, greedy and
-temperature/top-k sampling.
+temperature / top-k / top-p sampling (``sampler="hip"``: ops.sample_logits,
+one launch per step, also inside the graphed decoder).
 
 Scope: tp=1 (single device).  At tp=1 the Col/Row parallel linears, SP
 plumbing and vocab-parallel head are all inert, so the training modules'
@@ -22,7 +23,8 @@ from typing import List, Optional, Tuple
 
 import torch
 
-from ..ops import Fp8KV, PagedKV, resolve_decode_attn_impl
+from ..ops import (Fp8KV, PagedKV, resolve_decode_attn_impl,
+                   sample_logits)
 from ..parallel.tensor import get_tp_size
 
 
@@ -114,6 +116,17 @@ def _sample(logits: torch.Tensor, greedy: bool, temperature: float,
     return torch.multinomial(probs, 1).squeeze(-1)
 
 
+def resolve_sampler(sampler: Optional[str] = None) -> str:
+    """``"torch"`` (``_sample``: topk, masked_fill, softmax, multinomial; no
+    top-p) or ``"hip"`` (ops.sample_logits on uniform numbers drawn with
+    ``torch.rand``).  ``None`` reads ``TDPA_SAMPLER`` (default torch)."""
+    if sampler is None:
+        sampler = os.environ.get("TDPA_SAMPLER", "torch")
+    if sampler not in ("torch", "hip"):
+        raise ValueError(f"sampler must be 'torch' or 'hip', got {sampler!r}")
+    return sampler
+
+
 def decode_forward(model, idx: torch.Tensor, caches, pos0,
                    all_logits: bool = False, attn_impl: Optional[str] = None,
                    mask: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -157,7 +170,14 @@ class GraphedDecoder:
     reads the table's contents on the device, so the host may rewrite them in
     place between replays.
 
-    Greedy only (the argmax lives inside the graph).  Works for either
+    Greedy by default (the argmax lives inside the graph).  With any of
+    ``temperature`` / ``top_k`` / ``top_p`` / ``seed`` set, the captured step
+    ends in ops.sample_logits instead, writing the next token straight into
+    the input buffer: the parameters are (B,) device tensors this decoder
+    owns (``set_sampling`` rewrites them in place, no recapture) and the
+    uniform numbers ``self.u`` are refilled from the decoder's own
+    ``torch.Generator`` (seeded with ``seed``) before every replay, one small
+    launch outside the graph.  ``top_k=1`` is greedy.  Works for either
     model family (``GraphedGPT2Decoder`` and ``GraphedLlamaDecoder`` are
     this class); usage::
 
@@ -169,7 +189,11 @@ class GraphedDecoder:
                  attn_impl: Optional[str] = None,
                  kv_dtype: Optional[str] = None,
                  kv_layout: Optional[str] = None,
-                 page_size: Optional[int] = None):
+                 page_size: Optional[int] = None,
+                 temperature: Optional[float] = None,
+                 top_k: Optional[int] = None,
+                 top_p: Optional[float] = None,
+                 seed: Optional[int] = None):
         assert get_tp_size() == 1
         self.attn_impl = resolve_decode_attn_impl(attn_impl)
         assert torch.cuda.is_available()
@@ -184,6 +208,18 @@ class GraphedDecoder:
         self.pos_t = torch.zeros(1, dtype=torch.long, device=dev)
         self.pos = 0
         self.mask = None                # the hip path reads pos_t instead
+        self.sampled = any(v is not None
+                           for v in (temperature, top_k, top_p, seed))
+        if self.sampled:
+            self.u = torch.zeros(batch, dtype=torch.float32, device=dev)
+            self.temperature = torch.ones(batch, dtype=torch.float32,
+                                          device=dev)
+            self.top_k = torch.zeros(batch, dtype=torch.int32, device=dev)
+            self.top_p = torch.ones(batch, dtype=torch.float32, device=dev)
+            self.set_sampling(temperature, top_k, top_p)
+            self.generator = torch.Generator(device=dev)
+            if seed is not None:
+                self.generator.manual_seed(seed)
         # capture with position 0 visible (an all-masked row would NaN);
         # the garbage this warmup writes into cache slot 0 is overwritten
         # by the first prefill()
@@ -208,7 +244,28 @@ class GraphedDecoder:
                                 self.pos_t, attn_impl=self.attn_impl,
                                 mask=self.mask)             # (B, V)
         self._logits = logits
-        self.in_tok.copy_(logits.argmax(-1, keepdim=True))
+        self._next_token(logits)
+
+    def _next_token(self, logits):
+        if self.sampled:
+            sample_logits(logits, self.u, self.temperature, self.top_k,
+                          self.top_p, out=self.in_tok)
+        else:
+            self.in_tok.copy_(logits.argmax(-1, keepdim=True))
+
+    def set_sampling(self, temperature: Optional[float] = None,
+                     top_k: Optional[int] = None,
+                     top_p: Optional[float] = None):
+        """Rewrite the sampling parameters of a sampled decoder in place (a
+        scalar, or a (B,) tensor for per-row values); None leaves one as it
+        is.  The captured graph reads them on the device."""
+        assert self.sampled, "this decoder was captured greedy"
+        for buf, v in ((self.temperature, temperature), (self.top_k, top_k),
+                       (self.top_p, top_p)):
+            if isinstance(v, torch.Tensor):
+                buf.copy_(v)
+            elif v is not None:
+                buf.fill_(v)
 
     @torch.no_grad()
     def prefill(self, idx: torch.Tensor):
@@ -223,7 +280,9 @@ class GraphedDecoder:
             self.mask.fill_(float("-inf"))
             self.mask[..., :S0 + 1] = 0
         self.pos_t.fill_(S0)
-        self.in_tok.copy_(logits.argmax(-1, keepdim=True))
+        if self.sampled:
+            self.u.uniform_(generator=self.generator)
+        self._next_token(logits)
 
     @torch.no_grad()
     def step(self) -> torch.Tensor:
@@ -231,6 +290,8 @@ class GraphedDecoder:
         the one the PREVIOUS forward predicted; this replay consumes it."""
         assert self.pos < self.max_seq, "decoder cache is full"
         tok = self.in_tok[:, 0].clone()
+        if self.sampled:
+            self.u.uniform_(generator=self.generator)
         self._graph.replay()
         self.pos += 1
         self.pos_t += 1
@@ -258,7 +319,10 @@ def generate(model, idx: torch.Tensor, max_new_tokens: int,
              attn_impl: Optional[str] = None,
              kv_dtype: Optional[str] = None,
              kv_layout: Optional[str] = None,
-             page_size: Optional[int] = None) -> torch.Tensor:
+             page_size: Optional[int] = None,
+             top_p: Optional[float] = None,
+             sampler: Optional[str] = None,
+             generator: Optional[torch.Generator] = None) -> torch.Tensor:
     """Autoregressive generation with KV caches.
 
     Args:
@@ -274,8 +338,19 @@ def generate(model, idx: torch.Tensor, max_new_tokens: int,
             ``page_size`` positions per page; needs ``attn_impl="hip"``);
             ``None`` reads ``TDPA_KV_LAYOUT`` and ``TDPA_KV_PAGE`` (default
             contiguous, 16).
+        top_p: nucleus mass; needs ``sampler="hip"``.
+        sampler: with ``greedy=False``, ``"torch"`` (``_sample``) or
+            ``"hip"`` (ops.sample_logits on ``torch.rand(B,
+            generator=generator)``); ``None`` reads ``TDPA_SAMPLER``
+            (default torch).
+        generator: the ``torch.Generator`` of the ``"hip"`` sampler's
+            uniform numbers, on the logits' device (None: the default one).
     Returns (B, S0 + max_new_tokens) token ids.
     """
+    sampler = resolve_sampler(sampler)
+    if top_p is not None and sampler == "torch":
+        raise ValueError("top_p needs sampler=\"hip\" (the torch sampler "
+                         "has no nucleus step)")
     assert get_tp_size() == 1, "generate() supports tp=1 (single device)"
     B, S0 = idx.shape
     total = S0 + max_new_tokens
@@ -287,7 +362,13 @@ def generate(model, idx: torch.Tensor, max_new_tokens: int,
     for _ in range(max_new_tokens):
         logits = decode_forward(model, chunk, caches, pos0,
                                 attn_impl=attn_impl)
-        nxt = _sample(logits, greedy, temperature, top_k)
+        if greedy or sampler == "torch":
+            nxt = _sample(logits, greedy, temperature, top_k)
+        else:
+            if logits.dtype not in (torch.bfloat16, torch.float32):
+                logits = logits.float()
+            u = torch.rand(B, generator=generator, device=logits.device)
+            nxt = sample_logits(logits, u, temperature, top_k, top_p)
         tokens = torch.cat([tokens, nxt[:, None]], dim=1)
         pos0 += chunk.shape[1]
         chunk = nxt[:, None]

@@ -1295,3 +1295,9 @@ from .int4 import (Int4Weight, int4_linear, is_int4_linear,  # noqa: E402
 from . import paged_kv  # noqa: E402
 from .kv_fp8 import Fp8KV, quantize_kv_rows  # noqa: E402
 from .paged_kv import PagedKV, kv_cache_append  # noqa: E402
+
+# ---------------------------------------------------------------------------
+# fused temperature / top-k / top-p sampling
+# ---------------------------------------------------------------------------
+
+from .sample import sample_logits  # noqa: E402

@@ -36,6 +36,7 @@ SOURCES = [
     "chunk_attn.hip",
     "grouped_gemm.hip",
     "moe_route.hip",
+    "sample.hip",
 ]
 
 # A second module, ``_tdpa_nopk``: translation units built without

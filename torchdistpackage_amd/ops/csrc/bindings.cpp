@@ -125,6 +125,9 @@ torch::Tensor moe_route_gather(torch::Tensor y, torch::Tensor dest,
 std::tuple<torch::Tensor, c10::optional<torch::Tensor>> moe_route_scatter(
     torch::Tensor x, torch::Tensor dest, c10::optional<torch::Tensor> gates,
     c10::optional<torch::Tensor> y);
+torch::Tensor sample_logits(torch::Tensor logits, torch::Tensor u,
+                            torch::Tensor temperature, torch::Tensor top_k,
+                            torch::Tensor top_p, torch::Tensor out);
 std::vector<torch::Tensor> bias_residual_layernorm_fwd(
     torch::Tensor y, c10::optional<torch::Tensor> bias, torch::Tensor x_res,
     torch::Tensor ln_w, torch::Tensor ln_b, double eps);
@@ -219,6 +222,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "(x (N,D), dest, gates|None, y|None) -> (out (N*k,D), dgates|None): "
         "out[dest] = gates * x, dgates = x . y[dest]");
   m.attr("MOE_PLAN_CHUNK") = MOE_PLAN_CHUNK;
+  m.def("sample_logits", &sample_logits,
+        "(logits (B,V) bf16|fp32, u (B,) fp32, temperature (B,) fp32, top_k "
+        "(B,) int32, top_p (B,) fp32, out (B,) int64) -> out: one token per "
+        "row");
   m.def("bias_residual_layernorm_fwd", &bias_residual_layernorm_fwd,
         "(y, bias|None, x_res, ln_w, ln_b, eps) -> (x_new, h, mean, rstd)");
   m.def("layernorm_bwd_residual", &layernorm_bwd_residual,
