@@ -24,7 +24,11 @@ permuted table) on the hip route, ms/token at 4096/2048, B = 1 and 8.
 ``--sample`` runs the sampling A/B (scripts/kbench_sample.py): graphed greedy
 against graphed sampled decode (ops.sample_logits inside the graph) and eager
 ``generate`` with ``sampler="torch"`` against ``"hip"``, ms/token at
-4096/2048, B = 1 and 8."""
+4096/2048, B = 1 and 8.
+
+``--fused-decode`` runs the fused decode step A/B (scripts/
+kbench_fused_decode.py): ``TDPA_FUSED_DECODE`` off against on, bf16 and int4
+weights, graphed ms/token at 4096/2048, B = 1 and 8."""
 import argparse
 import os
 import sys
@@ -48,6 +52,7 @@ ap.add_argument("--chunk-attn", action="store_true")
 ap.add_argument("--kv-fp8", action="store_true")
 ap.add_argument("--kv-paged", action="store_true")
 ap.add_argument("--sample", action="store_true")
+ap.add_argument("--fused-decode", action="store_true")
 ap.add_argument("--attn-impl", default="hip", choices=("hip", "sdpa"))
 args = ap.parse_args()
 m = LlamaModel(llama3_8b(), device=dev, dtype=torch.bfloat16).eval()
@@ -87,6 +92,12 @@ if args.sample:
     from kbench_sample import end_to_end
     end_to_end(m)
     print("LLAMA SAMPLE AB OK")
+    sys.exit(0)
+
+if args.fused_decode:
+    from kbench_fused_decode import end_to_end
+    end_to_end(m)
+    print("LLAMA FUSED DECODE AB OK")
     sys.exit(0)
 
 for B in (1, 8):

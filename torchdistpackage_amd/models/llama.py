@@ -19,6 +19,7 @@ from typing import List, Optional
 import torch
 import torch.nn as nn
 
+from .. import ops
 from ..ops import RMSNorm, flash_attention, rope_rotate_half, swiglu
 from ..ops.gemm import linear as fast_linear
 from ..parallel.tensor.attn import _cached_attention
@@ -151,6 +152,19 @@ class LlamaAttention(nn.Module):
         def view4(t, nh):
             return t.reshape(S, B, nh, self.hd).permute(1, 2, 0, 3)
 
+        if (ops.fused_decode_enabled() and self.hd in (64, 128)
+                and all(torch.is_tensor(c) and c.is_cuda
+                        and c.dtype == torch.bfloat16
+                        for c in (q, k_cache, v_cache))):
+            # fused decode step: RoPE on q and k and both cache writes in
+            # one launch (fp8 and paged caches keep rope + kv_cache_append)
+            q = ops.rope_kv_append(view4(q, self.nh_local),
+                                   view4(k, self.nkv_local),
+                                   view4(v, self.nkv_local), self.rope.cos,
+                                   self.rope.sin, k_cache, v_cache, pos0)
+            return self.wo(_cached_attention(q, None, None, k_cache, v_cache,
+                                             pos0, self.causal, attn_impl,
+                                             mask, appended=True))
         q = self.rope(view4(q, self.nh_local), pos0)
         k = self.rope(view4(k, self.nkv_local), pos0)
         v = view4(v, self.nkv_local)
@@ -178,6 +192,13 @@ class LlamaMlp(nn.Module):
             x = copy_to_tp_region(x)
         return self.w2(swiglu(fast_linear(x, self.w1.weight),
                               fast_linear(x, self.w3.weight)))
+
+    @torch.no_grad()
+    def decode_step(self, x):
+        """The fused decode step's MLP (tp=1): the gate and up GEMVs and the
+        SwiGLU are one launch where ops.swiglu_linear has a kernel, the
+        composition of ``forward`` elsewhere (quantised weights, M > 8)."""
+        return self.w2(ops.swiglu_linear(x, self.w1.weight, self.w3.weight))
 
 
 class LlamaBlock(nn.Module):
@@ -210,10 +231,27 @@ class LlamaBlock(nn.Module):
 
     @torch.no_grad()
     def decode_step(self, x, k_cache, v_cache, pos0, attn_impl=None,
-                    mask=None):
-        x = x + self.attn.decode_step(self.attn_norm(x), k_cache, v_cache,
-                                      pos0, attn_impl, mask)
-        return x + self.mlp(self.mlp_norm(x))
+                    mask=None, y=None, defer=False):
+        """One cached step of the block.  With the fused decode step on
+        (ops.set_fused_decode) the residual stream travels as ``(x, y)``,
+        ``y`` a branch output not yet added (None: nothing pending): each add
+        runs inside the norm that follows it (ops.add_rms_norm), and with
+        ``defer`` the MLP output is handed back un-added, as ``(x, y)``, for
+        the next block's norm or the head's to absorb."""
+        if not ops.fused_decode_enabled():
+            assert y is None and not defer, "(x, y) is the fused decode step"
+            x = x + self.attn.decode_step(self.attn_norm(x), k_cache, v_cache,
+                                          pos0, attn_impl, mask)
+            return x + self.mlp(self.mlp_norm(x))
+        if y is None:
+            h = self.attn_norm(x)
+        else:
+            x, h = ops.add_rms_norm(x, y, self.attn_norm.weight,
+                                    self.attn_norm.eps)
+        y = self.attn.decode_step(h, k_cache, v_cache, pos0, attn_impl, mask)
+        x, h = ops.add_rms_norm(x, y, self.mlp_norm.weight, self.mlp_norm.eps)
+        y = self.mlp.decode_step(h)
+        return (x, y) if defer else x + y
 
 
 class LlamaEmbedding(nn.Module):
@@ -277,6 +315,16 @@ class LlamaHead(nn.Module):
             return fast_linear(x, self.weight).transpose(0, 1)
         return fast_linear(self.norm(x), self.weight).transpose(0, 1)
 
+    @torch.no_grad()
+    def decode(self, x, y=None):
+        """The head of the fused decode step (tp=1): the final norm absorbs
+        the last residual add ``x + y``."""
+        assert not self.vocab_parallel
+        if y is None:
+            return self.forward(x)
+        _, h = ops.add_rms_norm(x, y, self.norm.weight, self.norm.eps)
+        return fast_linear(h, self.weight).transpose(0, 1)
+
 
 class LlamaModel(nn.Module):
     def __init__(self, cfg: LlamaConfig, device=None, dtype=None):
@@ -323,6 +371,17 @@ class LlamaModel(nn.Module):
         """KV-cache forward of ``idx`` (B, S_new) at ``pos0``; arguments
         and result as GPT2Model.decode_forward."""
         x = self.embed.tok(idx).transpose(0, 1).contiguous()
+        if ops.fused_decode_enabled():
+            # the residual stream as (x, y), y the last branch output not yet
+            # added: every add runs inside the norm that follows it
+            y = None
+            for blk, (kc, vc) in zip(self.blocks, caches):
+                x, y = blk.decode_step(x, kc, vc, pos0, attn_impl, mask,
+                                       y=y, defer=True)
+            if not all_logits:
+                x, y = x[-1:], (None if y is None else y[-1:])
+            logits = self.head.decode(x, y)
+            return logits if all_logits else logits[:, -1]
         for blk, (kc, vc) in zip(self.blocks, caches):
             x = blk.decode_step(x, kc, vc, pos0, attn_impl, mask)
         if all_logits:

@@ -1301,3 +1301,11 @@ from .paged_kv import PagedKV, kv_cache_append  # noqa: E402
 # ---------------------------------------------------------------------------
 
 from .sample import sample_logits  # noqa: E402
+
+# ---------------------------------------------------------------------------
+# fused glue of the Llama decode step: GEMV+SwiGLU, RoPE+cache append,
+# residual add+RMSNorm
+# ---------------------------------------------------------------------------
+
+from .fused_decode import (add_rms_norm, fused_decode_enabled,  # noqa: E402
+                           rope_kv_append, set_fused_decode, swiglu_linear)

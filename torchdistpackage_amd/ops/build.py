@@ -37,6 +37,7 @@ SOURCES = [
     "grouped_gemm.hip",
     "moe_route.hip",
     "sample.hip",
+    "fused_decode.hip",
 ]
 
 # A second module, ``_tdpa_nopk``: translation units built without

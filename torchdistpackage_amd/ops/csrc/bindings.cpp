@@ -147,6 +147,14 @@ void attn_bwd_dkdv(torch::Tensor dout, torch::Tensor q, torch::Tensor k,
                    torch::Tensor v, torch::Tensor lse, torch::Tensor delta,
                    torch::Tensor dk, torch::Tensor dv, bool causal,
                    double scale);
+torch::Tensor gemv_swiglu(torch::Tensor x, torch::Tensor w_gate,
+                          torch::Tensor w_up);
+torch::Tensor rope_kv_append(torch::Tensor q, torch::Tensor k, torch::Tensor v,
+                             torch::Tensor cs, torch::Tensor sn,
+                             torch::Tensor k_cache, torch::Tensor v_cache,
+                             c10::optional<torch::Tensor> pos_t, long pos0);
+std::vector<torch::Tensor> add_rmsnorm(torch::Tensor x, torch::Tensor y,
+                                       torch::Tensor w, double eps);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rmsnorm_fwd", &rmsnorm_fwd);
@@ -245,4 +253,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_bwd_dkdv", &attn_bwd_dkdv,
         "(dout, q, k, v, lse, delta, dk, dv, causal, scale): the dk/dv stage "
         "of the head-dim-128 backward alone, under the current knobs");
+  m.def("gemv_swiglu", &gemv_swiglu,
+        "(x (M,K), w_gate (N,K), w_up (N,K)) bf16 -> (M,N) bf16: "
+        "silu(x @ w_gate^T) * (x @ w_up^T), 1 <= M <= 8");
+  m.def("rope_kv_append", &rope_kv_append,
+        "(q, k, v, cos, sin, k_cache, v_cache, pos_t|None, pos0) -> rotated "
+        "q; rotated k and v go into the caches at [pos, pos + S)");
+  m.def("add_rmsnorm", &add_rmsnorm,
+        "(x, y, weight, eps) -> (bf16(x + y), rms_norm of that)");
 }

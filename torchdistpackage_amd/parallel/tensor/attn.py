@@ -63,7 +63,8 @@ _CHUNK_MAX_ROWS = 64
 def _cached_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
                       k_cache: torch.Tensor, v_cache: torch.Tensor, pos0,
                       causal: bool, attn_impl: Optional[str] = None,
-                      mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+                      mask: Optional[torch.Tensor] = None,
+                      appended: bool = False) -> torch.Tensor:
     """The one KV-cache attention step behind every ``decode_step``.
 
     q (B, H, S, hd) and k, v (B, Hkv, S, hd), RoPE already applied; writes
@@ -95,6 +96,10 @@ def _cached_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     A pair of ops.PagedKV takes the same branches: kv_cache_append writes
     through the block table, decode_attention runs its paged kernel, and the
     prefill route reads ``gather(pos0 + S)`` as a transient dense copy.
+
+    ``appended=True`` says the caller has already written the new rows into
+    the caches (ops.rope_kv_append): the write is skipped, ``k`` and ``v``
+    are not looked at, and nothing else changes.
     """
     B, H, S, hd = q.shape
     hip = resolve_decode_attn_impl(attn_impl) == "hip"
@@ -117,7 +122,9 @@ def _cached_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
         if not hip and mask is None:
             raise ValueError("tensor pos0 with attn_impl='sdpa' needs the "
                              "cache visibility mask")
-    if fp8 or paged:
+    if appended:
+        pass
+    elif fp8 or paged:
         ops.kv_cache_append(k_cache, v_cache, k, v, pos0)
     elif on_device:
         k_cache.index_copy_(2, pos0, k)
